@@ -21,6 +21,12 @@ Modes (other BASELINE configs):
                          cross-rank any-done all-reduce, masked gym reset kernel); on one
                          GPU the K gym steps are replayed from a hipGraph too
 
+A plain run does what the headline figure needs: set-up, warm-up, the K timed steps, the line.
+  --full                 also the untimed eager pass (per-step event times), the roofline block
+                         (FLOP count on the CPU oracle, committed PMC profile), the CPU
+                         baseline and the finite-obs check (null in the line without it)
+  --dump-outputs DIR     the State the last timed step left, as DIR/<name>.npy
+
 Multi-GPU: one process per GPU (torchrun); barrier + synchronize bracket the K timed steps
 and the max over ranks is reported.  Rank 0 prints ONE JSON line.
 """
@@ -118,6 +124,14 @@ def main() -> int:
     ap.add_argument("--legacy-spring", action="store_true",
                     help="brax <= 0.0.12 spring/impulse dynamics (the physics notebooks/ant_tag.ipynb:449 "
                          "pins) instead of PBD")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the untimed eager pass (per-step "
+                         "event times), the roofline block (FLOP count on the CPU oracle, committed PMC profile), "
+                         "the CPU baseline and the finite-obs check; without it these fields of the line are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the State the last timed step left (qp, obs, reward, done, "
+                         "metrics, info) as DIR/<name>.npy, float32 / float64; above 60 MB a fixed seeded sample of "
+                         "the env rows (DIR/sample_rows.npy holds their indices)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -203,11 +217,13 @@ def main() -> int:
     gatherer = ObsGatherer(total, obs_of().shape[-1], device=dev) if do_gather else None
     gather_ev = []  # (start, end) events of each timed step's all-gather (side stream)
 
+    returned = [state]  # what the last eager step returned to its caller (--dump-outputs)
+
     def one_step(t):
         if gym is not None:
             gym.step(act_at(t))
         else:
-            env.step_(state, act_at(t))
+            returned[0] = env.step_(state, act_at(t))
         if gatherer is not None:  # step t's obs gathered on the side stream during step t + 1
             gatherer.submit(obs_of())
 
@@ -271,14 +287,18 @@ def main() -> int:
     if world > 1:
         dist.barrier()
     wall = time.perf_counter() - t0
-    if roll is not None and gym is None and not args.policy_mlp:  # untimed: per-step kernel durations
+    dumped = None
+    if args.dump_outputs:  # the State as the last timed step left it (before the untimed pass below)
+        last = gym._state if gym is not None else (roll.state if roll is not None else returned[0])
+        dumped = dump_outputs(args.dump_outputs, last, MIXED if args.env == "mixed" else None, rank, world)
+    eager_pass = args.full and roll is not None and gym is None and not args.policy_mlp
+    if eager_pass:  # untimed: per-step kernel durations
         for k in range(args.steps):
             ev_a[k].record()
             one_step(args.warmup + k)
             ev_b[k].record()
         torch.cuda.synchronize()
-    per = ([ev_a[k].elapsed_time(ev_b[k]) for k in range(args.steps)]
-           if roll is None or (gym is None and not args.policy_mlp) else [])
+    per = [ev_a[k].elapsed_time(ev_b[k]) for k in range(args.steps)] if roll is None or eager_pass else []
     eager_ms = sum(per) / len(per) if per else float("nan")
     # the dominant kernel's time per launch: from the graph replay (back-to-back launches, no
     # host gaps) when there is one -- an eager step's event pair also holds the host's launch
@@ -294,7 +314,7 @@ def main() -> int:
     gather_max = max(r[2] for r in table)
     ms_per_step = 1e3 * wall / args.steps
     value = total * args.steps / wall
-    finite = bool(torch.isfinite(obs_of()).all())
+    finite = bool(torch.isfinite(obs_of()).all()) if args.full else None
 
     if rank != 0:
         if world > 1:
@@ -304,9 +324,76 @@ def main() -> int:
 
     # roofline of the dominant kernel (k_step) on this rank: algorithmic FLOPs per launch
     # (the path is FP32-VALU bound, not HBM or MFMA) and bytes per launch
+    # (--full only: the FLOP count replays the workload on the CPU oracle, the rest rides on it)
+    kinds = list(zip(MIXED, mixed_sizes(B))) if args.env == "mixed" else [(args.env, B)]
+    build = build_identity()
+    roofline = roofline_of(args, kinds, B, lo, total, mask, kern_ms, eager_ms, roll is not None, gym is not None,
+                           build) if args.full else None
+
+    cpu = None
+    if args.full and not args.no_cpu_baseline and world == 1 and gym is None:
+        cpu = cpu_baseline("ant_heavenhell" if args.env == "mixed" else args.env, B, args.cpu_seconds,
+                           args.cpu_threads, legacy=args.legacy_spring)
+
+    par = f"env-shard x{world}" + (" (strong: global batch split)" if strong else " (weak: batch per GPU)")
+    line = {
+        "metric": HEADLINE_METRIC if (args.env == "ant_heavenhell" and strong and total == 65536 and gym is None
+                                      and not args.policy_mlp and not args.legacy_spring)
+                  else f"env-steps/sec {args.env} " + ("legacy_spring " if args.legacy_spring else "")
+                  + (f"global batch {total}" if strong else f"batch {args.batch}/GPU")
+                  + (f" with a {args.policy_mlp}-hidden MLP policy in the loop" if args.policy_mlp else "")
+                  + (f" + obs mask ({args.obs_mask})" if mask is not None else ""),
+        "value": round(value, 1), "unit": "env-steps/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+        "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{args.env} B={B}/GPU (global {total}), "
+                               + ("create_gym_env (AutoresetVmapGymWrapper, gym-side autoreset)"
+                                  if gym is not None else "create(batch_size=B) autoreset chain")
+                               + f", episode_length {args.episode_length}, "
+                               + ("legacy spring/impulse (brax <= 0.0.12)" if args.legacy_spring else "PBD")
+                               + " 10 substeps, random "
+                               "uniform(-1,1) actions (threefry)"
+                               + (f", kinds {dict(kinds)} in one launch" if args.env == "mixed" else "")
+                               + (", RCCL obs all-gather per step" if do_gather else "")
+                               + (f", obs mask '{args.obs_mask}' ({len(mask)} of {_OBS[args.env]} columns) "
+                                  "stored by the step kernel" if mask is not None else "")
+                               + (f", MLP policy (D x {args.policy_mlp} x 8, tanh) per step in the same graph"
+                                  if args.policy_mlp else ""),
+                   "env": args.env, "global_batch": total, "batch_per_gpu": B,
+                   "episode_length": args.episode_length, "qp_storage": args.qp_dtype, "parallelism": par,
+                   "dynamics": "legacy_spring" if args.legacy_spring else "pbd",
+                   "obs_mask": args.obs_mask, "obs_mask_columns": 0 if mask is None else len(mask),
+                   "path": "gym" if gym is not None else "brax",
+                   "launch": "hipGraph replay of the K steps" if roll is not None else "eager per step"},
+        "gpu_event_ms_per_step": round(kern_ms_max, 4),
+        "full": bool(args.full), "roofline": roofline, "cpu_baseline": cpu, "obs_finite": finite,
+        # what ran: the process group's size and each rank's device (so a reader can tell N ranks
+        # on N devices from N ranks sharing one)
+        "world_size": world, "dist_backend": args.dist_backend if world > 1 else None,
+        "rank_devices": ranks, "distinct_devices": len({r["device"] for r in ranks}),
+        "per_rank": per_rank_rows(table, ranks, do_gather),
+        "build": build, "outputs": dumped,
+    }
+    if do_gather:
+        # device time of one step's all-gather (side stream, max over ranks) and how much of
+        # it ran under the next step's kernel (rank 0's events; the table has every rank's)
+        line["obs_allgather_ms"] = round(gather_max, 4)
+        line["obs_allgather_bytes"] = total * obs_of().shape[-1] * 4
+        line["obs_allgather_overlap"] = overlap
+        line["obs_allgather_exposed_ms_per_step"] = round(max(0.0, ms_per_step - kern_ms_max), 4)
+    print(json.dumps(line))
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+    return 0
+
+
+def roofline_of(args, kinds, B: int, lo: int, total: int, mask, kern_ms: float, eager_ms: float, graph: bool,
+                gym: bool, build: dict) -> dict:
+    """--full: the roofline block of the rank-0 line (FLOP count on the CPU oracle, the committed
+    PMC profile of this build and config)."""
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     qb = 2 if args.qp_dtype == "f16" else 4
-    kinds = list(zip(MIXED, mixed_sizes(B))) if args.env == "mixed" else [(args.env, B)]
     bpe = sum(bytes_per_env_step(n, qb) * b for n, b in kinds) / B + 4 * (0 if mask is None else len(mask))
     fw = None
     try:
@@ -347,10 +434,10 @@ def main() -> int:
     roofline = {
         "bound": "valu", "achieved": round(tflops, 3), "peak": VALU_PEAK_TF, "unit": "TFLOP/s",
         "frac": round(tflops / VALU_PEAK_TF, 5), "traffic": None,
-        "kernel": kname + (" + gym any-done + k_reset(where done)" if gym is not None else "")
+        "kernel": kname + (" + gym any-done + k_reset(where done)" if gym else "")
                   + (" + policy MLP GEMMs (per-step replay time, not the step kernel alone)" if args.policy_mlp else ""),
         "kernel_ms": round(kern_ms, 4), "units_per_launch": B,
-        "kernel_ms_source": "hipGraph replay of the K timed steps / K" if roll is not None
+        "kernel_ms_source": "hipGraph replay of the K timed steps / K" if graph
                             else "HIP events around each eager step",
         "eager_event_ms": round(eager_ms, 4),
         "flops_per_env_step": round(f_exe, 1),
@@ -371,14 +458,13 @@ def main() -> int:
         "hbm": {"achieved": round(hbm_gbs, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": round(hbm_gbs / HBM_PEAK_GBS, 6)},
     }
-    build = build_identity()
     prof, stale = committed_profile(args.env, B, args.qp_dtype, args.legacy_spring, build["lib_sha256"],
                                     args.obs_mask)
-    if stale is not None and gym is None:  # a profile of this config, but of another build of libpob.so
+    if stale is not None and not gym:  # a profile of this config, but of another build of libpob.so
         roofline["traffic_stale_profile"] = (f"profiles/{stale['source']} profiled a different libpob.so "
                                              f"({(stale.get('build') or {}).get('lib_sha256', 'unrecorded')[:12]}); "
                                              "its counters are not reported for this build")
-    if prof is not None and gym is None:
+    if prof is not None and not gym:
         if prof.get("traffic_bytes"):
             roofline["traffic"] = prof["traffic_bytes"]
             roofline["traffic_source"] = (f"profiles/{prof['source']}: rocprofv3 --pmc FETCH_SIZE (x2, gfx950) + "
@@ -394,63 +480,75 @@ def main() -> int:
             roofline["valu_source"] = (f"profiles/{prof['source']}: SQ_INSTS_VALU per launch x 2 cycles / "
                                        f"({SIMDS} SIMDs x live kernel time x {CLK_MAX_GHZ} GHz); "
                                        "profiled_clock: / (SIMDs x GRBM_GUI_ACTIVE/8) of the profiled launch")
+    return roofline
 
-    cpu = None
-    if not args.no_cpu_baseline and world == 1 and gym is None:
-        cpu = cpu_baseline("ant_heavenhell" if args.env == "mixed" else args.env, B, args.cpu_seconds,
-                           args.cpu_threads, legacy=args.legacy_spring)
 
-    par = f"env-shard x{world}" + (" (strong: global batch split)" if strong else " (weak: batch per GPU)")
-    line = {
-        "metric": HEADLINE_METRIC if (args.env == "ant_heavenhell" and strong and total == 65536 and gym is None
-                                      and not args.policy_mlp and not args.legacy_spring)
-                  else f"env-steps/sec {args.env} " + ("legacy_spring " if args.legacy_spring else "")
-                  + (f"global batch {total}" if strong else f"batch {args.batch}/GPU")
-                  + (f" with a {args.policy_mlp}-hidden MLP policy in the loop" if args.policy_mlp else "")
-                  + (f" + obs mask ({args.obs_mask})" if mask is not None else ""),
-        "value": round(value, 1), "unit": "env-steps/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-        "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"{args.env} B={B}/GPU (global {total}), "
-                               + ("create_gym_env (AutoresetVmapGymWrapper, gym-side autoreset)"
-                                  if gym is not None else "create(batch_size=B) autoreset chain")
-                               + f", episode_length {args.episode_length}, "
-                               + ("legacy spring/impulse (brax <= 0.0.12)" if args.legacy_spring else "PBD")
-                               + " 10 substeps, random "
-                               "uniform(-1,1) actions (threefry)"
-                               + (f", kinds {dict(kinds)} in one launch" if args.env == "mixed" else "")
-                               + (", RCCL obs all-gather per step" if do_gather else "")
-                               + (f", obs mask '{args.obs_mask}' ({len(mask)} of {_OBS[args.env]} columns) "
-                                  "stored by the step kernel" if mask is not None else "")
-                               + (f", MLP policy (D x {args.policy_mlp} x 8, tanh) per step in the same graph"
-                                  if args.policy_mlp else ""),
-                   "env": args.env, "global_batch": total, "batch_per_gpu": B,
-                   "episode_length": args.episode_length, "qp_storage": args.qp_dtype, "parallelism": par,
-                   "dynamics": "legacy_spring" if args.legacy_spring else "pbd",
-                   "obs_mask": args.obs_mask, "obs_mask_columns": 0 if mask is None else len(mask),
-                   "path": "gym" if gym is not None else "brax",
-                   "launch": "hipGraph replay of the K steps" if roll is not None else "eager per step"},
-        "gpu_event_ms_per_step": round(kern_ms_max, 4),
-        "roofline": roofline, "cpu_baseline": cpu, "obs_finite": finite,
-        # what ran: the process group's size and each rank's device (so a reader can tell N ranks
-        # on N devices from N ranks sharing one)
-        "world_size": world, "dist_backend": args.dist_backend if world > 1 else None,
-        "rank_devices": ranks, "distinct_devices": len({r["device"] for r in ranks}),
-        "per_rank": per_rank_rows(table, ranks, do_gather),
-        "build": build,
-    }
-    if do_gather:
-        # device time of one step's all-gather (side stream, max over ranks) and how much of
-        # it ran under the next step's kernel (rank 0's events; the table has every rank's)
-        line["obs_allgather_ms"] = round(gather_max, 4)
-        line["obs_allgather_bytes"] = total * obs_of().shape[-1] * 4
-        line["obs_allgather_overlap"] = overlap
-        line["obs_allgather_exposed_ms_per_step"] = round(max(0.0, ms_per_step - kern_ms_max), 4)
-    print(json.dumps(line))
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-    return 0
+DUMP_MAX_BYTES = 60_000_000  # --dump-outputs: at most this much on disk (the .npy payloads)
+
+
+def output_arrays(state, kinds=None) -> dict:
+    """name -> device tensor (first dim: the env batch) of everything a caller of the timed path
+    holds after a step: the State's qp, obs, reward, done, metrics and the tensors of info (the
+    PRNG keys, the episode counters, the masked obs).  info's first_qp / first_obs are the reset
+    snapshot the autoreset copies from -- an input, not a result -- and are left out.  A mixed
+    run's per-kind States are prefixed with the kind's name."""
+    if kinds is not None:
+        out = {}
+        for kind, s in zip(kinds, state):
+            out.update({f"{kind}.{k}": v for k, v in output_arrays(s).items()})
+        return out
+    out = {"qp_pos": state.qp.pos, "qp_rot": state.qp.rot, "qp_vel": state.qp.vel, "qp_ang": state.qp.ang,
+           "obs": state.obs, "reward": state.reward, "done": state.done}
+    out.update({f"metrics_{k}": v for k, v in state.metrics.items()})
+    out.update({f"info_{k}": v for k, v in state.info.items()
+                if isinstance(v, torch.Tensor) and k != "first_obs" and v.dim() >= 1
+                and v.shape[0] == state.obs.shape[0]})
+    return out
+
+
+def dump_outputs(path: str, state, kinds, rank: int, world: int) -> dict:
+    """--dump-outputs: write output_arrays(state) as ``path/<name>.npy`` (``<name>.rank<r>.npy`` on
+    several ranks).  Floats, bools and the int32 counts go out as float32 (exact), the uint32 PRNG
+    keys as float64 (exact).  When all of it exceeds DUMP_MAX_BYTES only a sample of the env rows is
+    written, the same rows of every array: a sorted draw without replacement from
+    ``numpy.random.default_rng(0)``, its indices in ``sample_rows.npy`` (float64).  (A mixed run
+    samples each kind's batch with the same rule, ``<kind>.sample_rows.npy``.)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = output_arrays(state, kinds)
+    groups = {}  # arrays that share an env batch (a mixed run: one group per kind)
+    for name, t in arrays.items():
+        groups.setdefault(name.split(".")[0] + "." if kinds is not None else "", []).append((name, t))
+    row_bytes = {g: sum((8 if t.dtype == torch.uint32 else 4) * (t.numel() // max(1, t.shape[0])) for _, t in ts)
+                 for g, ts in groups.items()}
+    need = sum(row_bytes[g] * ts[0][1].shape[0] for g, ts in groups.items())
+    sfx = f".rank{rank}" if world > 1 else ""
+    written = nbytes = 0
+    rows_kept = {}
+    for g, ts in groups.items():
+        B = ts[0][1].shape[0]
+        rows = None
+        if need > DUMP_MAX_BYTES:  # every group keeps the same fraction of its rows
+            n = max(1, int(B * (DUMP_MAX_BYTES - 8 * B * len(groups)) / need))
+            rows = np.sort(np.random.default_rng(0).choice(B, size=min(n, B), replace=False))
+            np.save(os.path.join(path, f"{g}sample_rows{sfx}.npy"), rows.astype(np.float64))
+            nbytes += 8 * rows.size
+            written += 1
+            rows_t = torch.from_numpy(rows).to(ts[0][1].device)
+        rows_kept[g.rstrip(".") or "all"] = B if rows is None else int(rows.size)
+        for name, t in ts:
+            if t.dtype == torch.uint32:  # reinterpreted for the row gather, restored below
+                t = t.view(torch.int32)
+            if rows is not None:
+                t = t.index_select(0, rows_t)
+            if t.dtype == torch.int32 and arrays[name].dtype == torch.uint32:
+                a = (t.cpu().numpy().astype(np.int64) & 0xFFFFFFFF).astype(np.float64)
+            else:
+                a = t.to(torch.float32).cpu().numpy()
+            np.save(os.path.join(path, f"{name}{sfx}.npy"), a)
+            nbytes += a.nbytes
+            written += 1
+    return {"dir": path, "files": written, "bytes": nbytes, "rows": rows_kept}
 
 
 def gather_rank_stats(vals, world: int, device) -> list:
