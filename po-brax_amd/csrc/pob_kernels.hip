@@ -61,7 +61,12 @@ struct pob_env {
 // (test hook: POB_QUAD_FORCE_FIXUP=1 makes the fast launch hand every wave to the fix-up launch,
 // so the parity tests run the fix-up path on every env; an internal flags bit)
 #define POB_F_INT_FORCE_FIXUP (1u << 30)
-#define POB_F_INTERNAL (POB_F_STAGED | POB_F_INT_FORCE_FIXUP)
+// (test hook: POB_QUAD_BLOCK_CAP=n lowers the block-cooperative walk's item capacity per block
+// to n (1 .. QBW_CAP), so its overflow detection and hand-over to the fix-up launch run at
+// ordinary states; eight internal flags bits, 0 = the full capacity)
+#define POB_F_INT_BWCAP_SHIFT 20
+#define POB_F_INT_BWCAP_MASK (0xFFu << POB_F_INT_BWCAP_SHIFT)
+#define POB_F_INTERNAL (POB_F_STAGED | POB_F_INT_FORCE_FIXUP | POB_F_INT_BWCAP_MASK)
 #define POB_F_PUBLIC (POB_F_EPISODE | POB_F_AUTORESET | POB_F_ZERO_STEPS_ON_DONE)
 
 // ---------------------------------------------------------------------------- state
@@ -763,7 +768,11 @@ __device__ __forceinline__ void quad_store_dyn(const StatePtrs &in, const StateP
 // wave's first obs element) could be forged by a first_obs row that AUTORESET copies -- and
 // every wave of the fast launch writes its mark, so the array needs no initialisation; slices
 // of it serve concurrent launches on disjoint state slices (GraphRollout groups).
-template <int KIND, typename QT, bool LEG = false, int MODE = 0>
+// COOP (MODE 1, HH / TAG, 256-thread blocks: k_step_quad): the block's four waves pool the wall
+// walk (pob_quad.h qwalls_detect_block), with two block barriers per collide substep -- so no
+// wave of such a block leaves the substep loop early: a wave past the batch runs it as a replay
+// of env B - 1 with no items, an overflowed block runs it to the end, and both return after it.
+template <int KIND, typename QT, bool LEG = false, int MODE = 0, bool COOP = false>
 POB_D void step_quad_body(csys_t *Sp, const int B, const StatePtrs &in, const float *__restrict__ act,
                           const StatePtrs &out, const uint32_t flags, const int L, const int gt, float *lds,
                           const float *legtab) {
@@ -783,9 +792,13 @@ POB_D void step_quad_body(csys_t *Sp, const int B, const StatePtrs &in, const fl
   bool act_lane = b < B;
   // the wave's 16 envs are consecutive rows of every state array
   int b_first = (gt - lane) >> 2;
-  if (b_first >= B) return;  // (wave-uniform: a block's waves past the batch; no barrier follows)
+  const bool dead = b_first >= B;  // (wave-uniform: a block's waves past the batch)
+  if (!COOP && dead) return;       // (no barrier follows)
   if (MODE == 2 && out.ovf_mark[b_first] == 0) return;  // (not marked)
-  if (MODE == 1 && lane == 0) out.ovf_mark[b_first] = 0;  // (every wave: the passes that finish leave it)
+  if (MODE == 1 && lane == 0 && !dead) out.ovf_mark[b_first] = 0;  // (every wave: the passes that finish leave it)
+  // (COOP: a wave past the batch stays for the block's barriers -- every lane replays env B - 1
+  // from the last live wave's rows, as the lanes past the batch in that wave do, and stores nothing)
+  if (COOP && dead) b_first = ((B - 1) >> 4) << 4;
   int nenv = B - b_first < 16 ? B - b_first : 16;
   int le = b - b_first;
   // The physics runs on all 64 lanes (the wave walk's DPP / bpermute rounds need every lane):
@@ -972,6 +985,31 @@ POB_D void step_quad_body(csys_t *Sp, const int B, const StatePtrs &in, const fl
 #ifndef POB_QUAD_SLOW_OOL
 #define POB_QUAD_SLOW_OOL 1  // (with POB_QUAD_FAST_PASS: the slow pass's substep out of line)
 #endif
+    if constexpr (MODE == 1 && WALLS && COOP) {
+      // the fast launch, block-cooperative: every wave of the block runs every substep (two block
+      // barriers in each collide substep, qwalls_detect_block) and only then leaves -- a wave past
+      // the batch with nothing stored, an overflowed block (block-uniform) to the fix-up launch
+      const int capf = (int)((flags & POB_F_INT_BWCAP_MASK) >> POB_F_INT_BWCAP_SHIFT);
+      QBlock blk{lds + QPOOL_OFF, __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), 0,
+                 capf != 0 ? capf : QBW_CAP, dead, false};
+#pragma nounroll
+      for (int it = 0; it < 2 * iters; ++it) {
+#if POB_QUAD_PRIO == 1
+        const int lvl = (it * 4) / (2 * iters);
+        if (lvl == 0) __builtin_amdgcn_s_setprio(3);
+        else if (lvl == 1) __builtin_amdgcn_s_setprio(2);
+        else if (lvl == 2) __builtin_amdgcn_s_setprio(1);
+        else __builtin_amdgcn_s_setprio(0);
+#endif
+        qpbd_substep<WALLS, false, false, true>(Sp, LT, WT, bd, a, Ls, (it & 1) != 0, fric, nullptr, nullptr, &blk);
+      }
+      if (dead) return;
+      if (blk.ovf || (flags & POB_F_INT_FORCE_FIXUP)) {
+        if (lane == 0) out.ovf_mark[b_first] = 1;
+        return;
+      }
+      break;
+    }
     if (MODE == 1 && WALLS) {
       // the fast launch: the store only; a wave with an overflowing lane leaves the step to the
       // fix-up launch (nothing of its state is written: every output store follows the physics)
@@ -1235,18 +1273,21 @@ POB_D bool quad_block_marked(const int B, const uint8_t *mark, const int bt0) {
   }
   return any;
 }
-template <int KIND, typename QT, int MODE = 0>
+// COOP: the block-cooperative wall walk (MODE 1, HH / TAG; launched with 256-thread blocks only:
+// the walk's segments are the four waves' regions)
+template <int KIND, typename QT, int MODE = 0, bool COOP = false>
 __global__ __launch_bounds__(256, POB_QUAD_MIN_WAVES) void k_step_quad(const void *sysp, const int B,
                                                                        const StatePtrs in,
                                                                        const float *__restrict__ act,
                                                                        const StatePtrs out, const uint32_t flags,
                                                                        const int L) {
-  __shared__ float lds[QL_FLOATS * 256];
+  static_assert(!COOP || (MODE == 1 && (KIND == POB_HEAVENHELL || KIND == POB_TAG)), "the cooperative walk: fast launch, HH / TAG");
+  __shared__ __attribute__((aligned(16))) float lds[QL_FLOATS * 256];
   __shared__ __attribute__((aligned(16))) float legtab[POB_TAB_FLOATS];
   if (MODE == 2 && !quad_block_marked(B, out.ovf_mark, (int)(blockIdx.x * blockDim.x)))
     return;
   stage_leg_table((csys_t *)(size_t)sysp, legtab);
-  step_quad_body<KIND, QT, false, MODE>((csys_t *)(size_t)sysp, B, in, act, out, flags, L,
+  step_quad_body<KIND, QT, false, MODE, COOP>((csys_t *)(size_t)sysp, B, in, act, out, flags, L,
                                         (int)(blockIdx.x * blockDim.x + threadIdx.x), lds, legtab);
 }
 
@@ -2919,6 +2960,11 @@ static uint32_t quad_force_fixup() {
   const char *f = getenv("POB_QUAD_FORCE_FIXUP");
   return f && atoi(f) != 0 ? POB_F_INT_FORCE_FIXUP : 0u;
 }
+static uint32_t quad_block_cap() {
+  const char *f = getenv("POB_QUAD_BLOCK_CAP");
+  const int n = f ? atoi(f) : 0;
+  return n >= 1 && n < QBW_CAP ? (uint32_t)n << POB_F_INT_BWCAP_SHIFT : 0u;
+}
 template <typename QT>
 static void launch_step_quad(int kind, bool legacy, int n_cu, hipStream_t st, const void *sp, int B,
                              const StatePtrs &pi, const float *act, const StatePtrs &po, uint32_t flags, int L) {
@@ -2944,10 +2990,14 @@ static void launch_step_quad(int kind, bool legacy, int n_cu, hipStream_t st, co
   // without the caller's mark array the one-launch form)
   const bool split = quad_split_launch(kind) && po.ovf_mark != nullptr;
   flags |= split ? quad_force_fixup() : 0u;
+  // 256-thread blocks of HH / TAG: the fast launch's block-cooperative wall walk
+  const bool coop = split && bs == 256 && (kind == POB_HEAVENHELL || kind == POB_TAG);
+  flags |= coop ? quad_block_cap() : 0u;
   switch (kind) {
     case POB_HEAVENHELL:
       if (split) {
-        hipLaunchKernelGGL((k_step_quad<POB_HEAVENHELL, QT, 1>), g, b, 0, st, sp, B, pi, act, po, flags, L);
+        if (coop) hipLaunchKernelGGL((k_step_quad<POB_HEAVENHELL, QT, 1, true>), g, b, 0, st, sp, B, pi, act, po, flags, L);
+        else hipLaunchKernelGGL((k_step_quad<POB_HEAVENHELL, QT, 1>), g, b, 0, st, sp, B, pi, act, po, flags, L);
         hipLaunchKernelGGL((k_step_quad<POB_HEAVENHELL, QT, 2>), g, b, 0, st, sp, B, pi, act, po, flags, L);
       } else {
         hipLaunchKernelGGL((k_step_quad<POB_HEAVENHELL, QT>), g, b, 0, st, sp, B, pi, act, po, flags, L);
@@ -2963,7 +3013,8 @@ static void launch_step_quad(int kind, bool legacy, int n_cu, hipStream_t st, co
       break;
     case POB_TAG:
       if (split) {
-        hipLaunchKernelGGL((k_step_quad<POB_TAG, QT, 1>), g, b, 0, st, sp, B, pi, act, po, flags, L);
+        if (coop) hipLaunchKernelGGL((k_step_quad<POB_TAG, QT, 1, true>), g, b, 0, st, sp, B, pi, act, po, flags, L);
+        else hipLaunchKernelGGL((k_step_quad<POB_TAG, QT, 1>), g, b, 0, st, sp, B, pi, act, po, flags, L);
         hipLaunchKernelGGL((k_step_quad<POB_TAG, QT, 2>), g, b, 0, st, sp, B, pi, act, po, flags, L);
       } else {
         hipLaunchKernelGGL((k_step_quad<POB_TAG, QT>), g, b, 0, st, sp, B, pi, act, po, flags, L);

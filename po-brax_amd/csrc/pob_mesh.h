@@ -584,6 +584,7 @@ POB_D v3 mwall_world_n(const MWall &W, const v3 nl) {
 }
 
 #ifndef POB_MESH_HOST
+#include "pob_blockwalk.h"
 // ---------------------------------------------------------------- the wave's face walk
 // Walk the lanes' face items (M[s]: bit 8 w + f for face f of wall w of the lane's body slot
 // s; slots, then bits, in increasing order: the oracle's contact order per body) and call
@@ -866,6 +867,69 @@ POB_D void mesh_wave_walk(G &g, const float *WT, fcptr_t FC, const float cz, con
         if constexpr (HAND == 1) apply((t < 2 ? own1 : own2) && h != 0, s, t < 2 ? b1 : b2, tw, nn, dw);
         else if ((t < 2 ? own1 : own2) && h != 0) apply(s, t < 2 ? b1 : b2, tw, nn, dw);
       }
+    }
+  }
+}
+
+// The block-cooperative walk's evaluation (pob_blockwalk.h: the four waves of a block pool a
+// collide substep's items in LDS): this wave's rounds r0, r0 + 4, .. of the block's deal d,
+// group g of round r evaluating item 8 r + g with mesh_wave_walk's code -- the operands (the
+// owner's segment, radius, wall / face bits) from the item's LDS record instead of the owner
+// lane, so the same operations on the same bits -- and each triangle's winner lane writing the
+// contact (tau, world n, dist) or the no-contact mark into the owner segment's contact slot
+// fixed by (item, triangle) -- over the item's record, which this group alone read, above --:
+// every slot of an item is written exactly once, by one lane, no atomics.  xch = segment 0, wstride = floats between segments.  All 64 lanes active; the trip
+// count differs per wave (no block barrier inside).
+template <class G>
+POB_D void mesh_block_walk(G &g, const float *WT, fcptr_t FC, const float cz, const float hz, float *xch,
+                           const int wstride, const BwDeal &d, const int r0) {
+  const int lane = (int)__lane_id();
+  const int grp = lane >> 3, tri = (lane >> 2) & 1, kk = lane & 3;
+  const int R = bw_rounds(d);
+#pragma nounroll
+  for (int r = r0; r < R; r += QBW_WAVES) {
+    const int i = 8 * r + grp;
+    const bool gv = i < d.T;
+    int ow, j;
+    bw_item_owner(d, gv ? i : 0, ow, j);  // (an idle group recomputes item 0: R > 0 has one)
+    float *sg = xch + ow * wstride;
+    const float *rec = sg + bw_item_off(j);
+    const v3 Ao = V(rec[0], rec[1], rec[2]), Bo = V(rec[3], rec[4], rec[5]);
+    const float ro = rec[6];
+    const int mo = __float_as_int(rec[7]);
+    const bool sego = bw_meta_seg(mo);
+    const MWall W = mwall_row(WT + POB_WALL_FLOATS * ((mo >> 3) & 7));
+    fcptr_t fcw = FC + 3 * POB_FACE_FLOATS * ((mo >> 3) & 7);
+    const v3 La = mwall_local(W, cz, Ao);
+    const v3 Lb = sego ? mwall_local(W, cz, Bo) : La;
+    const MFace F = mface(g, mo & 7, mcap_seg(g, La, Lb), W.hx, W.hy, hz, fcw);
+    F3 Sc, Pc;
+    MCand c = mface_cand_quad(g, F, tri, gv ? kk : 7, Sc, Pc);
+    c.d2 = mcand_key(c.d2);
+    float dmin = c.d2;
+    int kmin = kk;
+    mlexmin_dpp<0xB1>(dmin, kmin);  // quad_perm [1, 0, 3, 2]
+    mlexmin_dpp<0x4E>(dmin, kmin);  // quad_perm [2, 3, 0, 1]
+    const int neq = msum_dpp<0x4E>(msum_dpp<0xB1>(c.d2 == dmin ? 1 : 0));
+    const float T = (ro * ro) * 1.00000095367431640625f;
+    const bool tie = gv && neq > 1 && dmin < T;
+    if (__any(tie)) {  // (rare: brax's average of the candidates at the minimum, as mesh_wave_walk)
+      F3 Ss = f3(0.0f, 0.0f, 0.0f), Ps = Ss;
+      float us = 0.0f, cnt = 0.0f;
+      mtie_add<0>(c.d2, dmin, Sc, Pc, c.u, Ss, Ps, us, cnt);
+      mtie_add<1>(c.d2, dmin, Sc, Pc, c.u, Ss, Ps, us, cnt);
+      mtie_add<2>(c.d2, dmin, Sc, Pc, c.u, Ss, Ps, us, cnt);
+      mtie_add<3>(c.d2, dmin, Sc, Pc, c.u, Ss, Ps, us, cnt);
+      if (tie && kk == kmin) c = bcand(f3(Ss.a / cnt, Ss.b / cnt, Ss.w / cnt), f3(Ps.a / cnt, Ps.b / cnt, Ps.w / cnt), us / cnt);
+    }
+    if (gv && kk == kmin) {
+      float tau = 0.0f, dst = 0.0f;
+      v3 nl, nw = V(0.0f, 0.0f, 0.0f);
+      const bool hit = mface_contact(g, F.k, c, ro, T, tau, nl, dst);
+      if (hit) nw = mwall_world_n(W, nl);
+      float *o = sg + bw_con_off(2 * j + tri);
+      o[0] = tau; o[1] = nw.x; o[2] = nw.y; o[3] = nw.z;
+      o[4] = hit ? dst : __int_as_float(QBW_NO_CONTACT);
     }
   }
 }

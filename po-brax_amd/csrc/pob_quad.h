@@ -180,6 +180,7 @@ struct QWalls {
   int nct;                // wall contacts of the position pass
   float c[6 * QK];        // the first QK: body, tau, n, dist (the re-walk builds, OVF)
   float seg[6 * QNB];     // nct > QK only: the segments a, b of the three bodies
+  int c0, c1;             // the block-cooperative walk only: the lane's contact slots [c0, c1)
 };
 #ifndef POB_QUAD_WAVE_WALK
 #define POB_QUAD_WAVE_WALK 1  // 1: the wave-cooperative face walk (pob_mesh.h mesh_wave_walk)
@@ -420,6 +421,9 @@ POB_D void qwalls_walk_pool(csys_t &S, const float *LT, const float *WT, const Q
              [&](const int l, v3 &A, v3 &B, float &r, bool &seg) { qpose_seg(S, LT, b, l, A, B, r, seg); }, sink);
   ws.nct += sink.nct;
   ovf = ovf | (sink.npool > QPOOL_N);
+  // (a wave whose pool overflowed discards the step; its lists are incomplete -- a lane whose
+  // first contact fell past the pool never wrote its head -- so the passes start from none)
+  if (sink.npool > QPOOL_N) ws.nct = 0;
 #if POB_QUAD_WALK_GACC
   ovf = ovf | g.bad();
 #endif
@@ -520,6 +524,110 @@ POB_D void qwalls_detect(csys_t *Sp, const float *LT, const float *WT, const QBo
       ws.seg[6 * l + 3] = ms.b[l].x; ws.seg[6 * l + 4] = ms.b[l].y; ws.seg[6 * l + 5] = ms.b[l].z;
     }
   }
+}
+
+// ------------------------------------------------ the block-cooperative detection
+// The fast launch's detection in 256-thread blocks (HH, TAG): the block's four waves pool the
+// substep's face items and share the walk rounds out evenly (pob_blockwalk.h) -- a round costs
+// the same with one item or eight, a wave's rounds are half empty on average, and the four
+// waves sit on the four SIMDs of one CU, whose walk load this evens out.
+//   1. cull per wave (as qwalls_detect); 2. publish: every lane writes its items' records into
+//   its wave's segment; BARRIER 1; 3. evaluate: each wave its share of the block's rounds, the
+//   winners writing the contact slots; BARRIER 2; 4. apply: the owners read their slots in walk
+//   order in the position and the velocity pass (qcontacts_position / _velocity, COOP).
+// Two barriers per collide substep suffice: between barrier 2 and the next barrier 1 a wave
+// reads (apply) and writes (the next publish) only its OWN segment, and the others touch that
+// segment only between a barrier 1 and the barrier 2 after it (evaluation: they read its
+// records and count, write its contact slots) -- so a fast wave's next publish cannot overtake
+// a slow wave's evaluation (that wave has passed barrier 2, its evaluation is over), and no
+// evaluation can start before every wave's publish is complete (barrier 1).  The same argument
+// covers the step's ends: the state staging before the first publish and the output staging
+// after the last apply use the wave's own region only.
+// Barrier discipline: every wave of the block calls this exactly once per collide substep and
+// executes both barriers whatever its items, its lanes past the batch, its overflow state --
+// a wave past the batch (dead) publishes no items and still evaluates its rounds; an overflow
+// (block-uniform: every wave derives it from the same four counts) only empties the deal.
+struct QBlock {
+  float *xch;  // segment 0 (the block's LDS + QPOOL_OFF; segment w at + w * 64 QL_FLOATS)
+  int w;       // the wave's number in the block
+  int sub;     // collide substeps done
+  int cap;     // the block's item capacity (QBW_CAP; lower: the POB_QUAD_BLOCK_CAP test hook)
+  bool dead;   // a wave past the batch
+  bool ovf;    // the block overflowed in some substep (block-uniform)
+};
+static_assert(QBW_SEG_FLOATS <= QL_FLOATS * 64 - QPOOL_OFF, "a wave's exchange segment fits its former contact pool");
+POB_D void qblock_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+POB_D void qwalls_detect_block(csys_t *Sp, const float *LT, const float *WT, const QBody &b, QWalls &ws, const QLds &L,
+                               QBlock &blk) {
+  csys_t &S = *launder(Sp);
+  uint64_t M[QNB];
+  {
+    const v3 rv_leg = qrot_xy(qcap_end(S, LT, 2, 0), b.q[2]);
+    QMesh ms;
+    qmesh_segments(S, LT, b, rv_leg, ms);
+    const uint32_t lw = qwall_mask(S, b);
+    qmesh_items(S, LT, WT, lw | (lw << 8) | (lw << 16), ms, M);
+  }
+  if (blk.dead) { M[0] = 0ull; M[1] = 0ull; M[2] = 0ull; }
+  // publish: the lanes' items in lane order, each lane's in walk order
+  float *own = L.pool();
+  const int nl = bw_lane_count(M[0], M[1], M[2]);
+  int base = 0, tot = 0;
+#pragma unroll
+  for (int bit = 0; bit < QBW_PREFIX_BITS; ++bit) bw_prefix_step(__ballot(((nl >> bit) & 1) != 0), L.t, bit, base, tot);
+  {
+    int at = base;
+#pragma nounroll
+    for (int k = 0; k < QBW_LANE_MAX; ++k) {
+      int s, bit;
+      const bool has = bw_next_item(M, s, bit);
+      if (!__any(has)) break;
+      v3 A, B;
+      float r;
+      bool seg;
+      qpose_seg(S, LT, b, s, A, B, r, seg);
+      if (has && at < QBW_WCAP) {
+        float *o = own + bw_item_off(at);
+        const float meta = __int_as_float(bw_meta(bit, seg, s));
+        o[0] = A.x; o[1] = A.y; o[2] = A.z; o[3] = B.x; o[4] = B.y; o[5] = B.z; o[6] = r; o[7] = meta;
+        o[2 * QBW_CON_DW] = meta;
+      }
+      ++at;
+    }
+  }
+  if (L.t == 0) own[bw_count_off()] = __int_as_float(tot);
+  qblock_barrier();  // BARRIER 1: every wave's records and count are in LDS
+  const int ws_f = QL_FLOATS * 64;
+  // (the four counts: the same words in every lane and wave -- held as scalars)
+  const int n0 = __builtin_amdgcn_readfirstlane(__float_as_int(blk.xch[bw_count_off()]));
+  const int n1 = __builtin_amdgcn_readfirstlane(__float_as_int(blk.xch[ws_f + bw_count_off()]));
+  const int n2 = __builtin_amdgcn_readfirstlane(__float_as_int(blk.xch[2 * ws_f + bw_count_off()]));
+  const int n3 = __builtin_amdgcn_readfirstlane(__float_as_int(blk.xch[3 * ws_f + bw_count_off()]));
+  const BwDeal d = bw_deal(n0, n1, n2, n3, blk.cap);
+  blk.ovf = blk.ovf | d.ovf;
+  {
+    GuardBranch g;
+    mesh_block_walk(g, WT, pob_face_table(S), S.wall_cz, S.wall_hz, blk.xch, ws_f, d, bw_first_round(blk.w, blk.sub));
+  }
+  qblock_barrier();  // BARRIER 2: every contact slot of the deal is written
+  ++blk.sub;
+  bw_apply_range(base, nl, d.ovf, ws.c0, ws.c1);
+  ws.nct = ws.c1 - ws.c0;
+}
+
+// The lane's next contact slot in [c, c1) that holds a contact (c1: none left).  The owners
+// skip their no-contact slots on their own, so every iteration of the passes' apply loops
+// carries a contact on each lane that has one left (iterations = the busiest lane's contacts,
+// as with the per-wave walk's lists, not its triangles).
+POB_D int qblock_next_hit(const float *sg, int c, const int c1) {
+#pragma unroll 1
+  while (true) {
+    const bool skip = c < c1 && __float_as_int(sg[bw_con_off(c) + QBW_CON_DW - 1]) == QBW_NO_CONTACT;
+    if (!__any(skip)) break;
+    c = skip ? c + 1 : c;
+  }
+  return c;
 }
 
 // One wall contact applied at the position level (penetration r - dist, the contact at the
@@ -625,7 +733,7 @@ POB_D void qwalls_rewalk_inl(csys_t &S, const float *LT, const float *WT, const 
 
 // Position pass of a collide substep: ground contacts (ground first per body, oracle order),
 // then the wall contacts from the store in detection order
-template <bool WALLS, bool OVF = true>
+template <bool WALLS, bool OVF = true, bool COOP = false>
 POB_D void qcontacts_position(csys_t *Sp, const float *LT, const float *WT, QBody &b, const QLds &L, QGround &gc,
                               const QWalls &ws, v3 (&DX)[QNB], v3 (&DA)[QNB], const float fric) {
   csys_t &S = *launder(Sp);
@@ -650,6 +758,21 @@ POB_D void qcontacts_position(csys_t *Sp, const float *LT, const float *WT, QBod
   q4 pq[QNB];
 #pragma unroll
   for (int l = 0; l < QNB; ++l) { px[l] = L.get3(l, QF_PX); pq[l] = L.get4(l, QF_PQ); }
+  if constexpr (COOP) {  // the block-cooperative walk: the lane's contact slots in its wave's segment, in walk order
+    const float *sg = L.pool();
+    int c = qblock_next_hit(sg, ws.c0, ws.c1);
+#pragma unroll 1
+    while (__any(c < ws.c1)) {
+      if (c < ws.c1) {
+        const float *p = sg + bw_con_off(c);
+        const int l = bw_meta_slot(__float_as_int(sg[bw_meta_off(c >> 1)]));
+        qwall_pos_one(g, S, SC, LT, b.x, b.q, px, pq, l, p[0], V(p[1], p[2], p[3]), p[4], DX, DA);
+        ++c;
+      }
+      c = qblock_next_hit(sg, c, ws.c1);
+    }
+    return;
+  }
 #if POB_QUAD_WAVE_WALK
   if (!OVF) {  // the fast pass: the lane's list in the wave's pool (a wave with an overflow runs the step again)
     const float *pool = L.pool();
@@ -705,7 +828,7 @@ POB_D void qcontacts_position(csys_t *Sp, const float *LT, const float *WT, QBod
 
 // Velocity pass: ground contacts, then the wall contacts from the store (contact points
 // x + tau rotate(e0, q) at the post-projection pose)
-template <bool WALLS, bool OVF = true>
+template <bool WALLS, bool OVF = true, bool COOP = false>
 POB_D void qcontacts_velocity(csys_t *Sp, const float *LT, const float *WT, QBody &b, const QGround &gc,
                               const QWalls &ws, const QLds &L, v3 (&dV)[QNB], v3 (&dW)[QNB], const float fric) {
   csys_t &S = *launder(Sp);
@@ -727,6 +850,21 @@ POB_D void qcontacts_velocity(csys_t *Sp, const float *LT, const float *WT, QBod
   return;  // timing experiment only: no velocity-pass wall contacts
 #endif
   POB_FENCE();
+  if constexpr (COOP) {
+    const float *sg = L.pool();
+    int c = qblock_next_hit(sg, ws.c0, ws.c1);
+#pragma unroll 1
+    while (__any(c < ws.c1)) {
+      if (c < ws.c1) {
+        const float *p = sg + bw_con_off(c);
+        const int l = bw_meta_slot(__float_as_int(sg[bw_meta_off(c >> 1)]));
+        qwall_vel_one(g, S, SC, LT, b.x, b.q, b.v, b.w, l, p[0], V(p[1], p[2], p[3]), p[4], dV, dW);
+        ++c;
+      }
+      c = qblock_next_hit(sg, c, ws.c1);
+    }
+    return;
+  }
 #if POB_QUAD_WAVE_WALK
   if (!OVF) {
     const float *pool = L.pool();
@@ -927,9 +1065,10 @@ POB_D float quad_friction(const csys_t &S) {
 // collide substep at the point the wall pass would (qwalls_detect) and reports a lane whose
 // mask is not empty in *near -- with every mask empty the wall pass finds no face item, so
 // the two passes compute the same bits.
-template <bool WALLS, bool CHECK = false, bool OVF = true>
+template <bool WALLS, bool CHECK = false, bool OVF = true, bool COOP = false>
 POB_D void qpbd_substep(csys_t *Sp, const float *LT, const float *WT, QBody &b, const float (&act)[QNJ], const QLds &L,
-                        const bool COLLIDE, const float fric, bool *near = nullptr, bool *ovf = nullptr) {
+                        const bool COLLIDE, const float fric, bool *near = nullptr, bool *ovf = nullptr,
+                        QBlock *blk = nullptr) {
 #pragma unroll
   for (int l = 0; l < QNB; ++l) { L.set3(l, QF_PX, b.x[l]); L.set4(l, QF_PQ, b.q[l]); }
   // 1. acceleration level.  Torso: dw0 = (((0 - t0) - t2) - t4) - t6 over the quad.
@@ -975,7 +1114,10 @@ POB_D void qpbd_substep(csys_t *Sp, const float *LT, const float *WT, QBody &b, 
   // 2b. wall contact detection (collide substeps), at the pose the projection starts from
   QWalls ws;
   ws.nct = 0;
-  if (COLLIDE) qwalls_detect<WALLS, OVF>(Sp, LT, WT, b, ws, L, ovf);
+  if constexpr (COOP) {
+    // (COLLIDE is block-uniform -- the substep's parity -- so the block's waves agree on the barriers)
+    if (COLLIDE) qwalls_detect_block(Sp, LT, WT, b, ws, L, *blk);
+  } else if (COLLIDE) qwalls_detect<WALLS, OVF>(Sp, LT, WT, b, ws, L, ovf);
   if (CHECK && COLLIDE) *near = *near | (qwall_mask(*launder(Sp), b) != 0u);
   // 3. position projection
   QGround gc;
@@ -1005,7 +1147,7 @@ POB_D void qpbd_substep(csys_t *Sp, const float *LT, const float *WT, QBody &b, 
       qtorso_add<2>(DX[0], DA[0], tq, imp0);
       qtorso_add<3>(DX[0], DA[0], tq, imp0);
     }
-    if (COLLIDE) qcontacts_position<WALLS, OVF>(Sp, LT, WT, b, L, gc, ws, DX, DA, fric);
+    if (COLLIDE) qcontacts_position<WALLS, OVF, COOP>(Sp, LT, WT, b, L, gc, ws, DX, DA, fric);
 #pragma unroll
     for (int l = 0; l < QNB; ++l) {
       b.x[l] = vadd(b.x[l], DX[l]);
@@ -1029,7 +1171,7 @@ POB_D void qpbd_substep(csys_t *Sp, const float *LT, const float *WT, QBody &b, 
     v3 dV[QNB], dW[QNB];
 #pragma unroll
     for (int l = 0; l < QNB; ++l) { dV[l] = V(0.0f, 0.0f, 0.0f); dW[l] = V(0.0f, 0.0f, 0.0f); }
-    qcontacts_velocity<WALLS, OVF>(Sp, LT, WT, b, gc, ws, L, dV, dW, fric);
+    qcontacts_velocity<WALLS, OVF, COOP>(Sp, LT, WT, b, gc, ws, L, dV, dW, fric);
 #pragma unroll
     for (int l = 0; l < QNB; ++l) {
       b.v[l] = vadd(b.v[l], dV[l]); b.w[l] = vadd(b.w[l], dW[l]);

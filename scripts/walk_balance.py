@@ -73,3 +73,60 @@ for t in range(1, S):
     bal.append(rounds_for(perm, items[t]).max())
     base.append(rounds_for(np.arange(Bn), items[t]).max())
 print(f"slowest wave rounds per step: identity {np.mean(base):.2f}, balanced by previous step {np.mean(bal):.2f}")
+
+# ---- the four-lane kernel (pob_quad.h): lane (env, leg k) holds three body slots -- the torso
+# (its items once per leg lane), Aux k+1, lower leg k -- 16 envs per wave, 64 per 256-thread block.
+# Per-wave walk (mesh_wave_walk): a round takes the next item of the first eight lanes holding
+# one and, with groups to spare, the second item of the same slot of lanes holding two.
+# Block-cooperative walk (pob_blockwalk.h): the block's T items make ceil(T / 8) rounds, wave w
+# takes the rounds r = (w + substep) mod 4, + 4, ..
+def lane_slots(rec_t):  # (B, NSUB, 9) -> (B, 4, NSUB, 3): per lane and slot
+    Bn = rec_t.shape[0]
+    out = np.zeros((Bn, 4, rec_t.shape[1], 3), np.int64)
+    for k in range(4):
+        out[:, k, :, 0] = rec_t[:, :, 0]
+        out[:, k, :, 1] = rec_t[:, :, 2 * k + 1]
+        out[:, k, :, 2] = rec_t[:, :, 2 * k + 2]
+    return out
+def wave_rounds(slots):  # (64, 3) item counts of a wave's lanes in a substep -> rounds of the per-wave walk
+    s = [list(x) for x in slots if x.sum() > 0]
+    rounds = 0
+    while s:
+        rounds += 1
+        n1 = len(s)
+        spare = 8 - min(8, n1)
+        for i, x in enumerate(s):
+            if i >= 8: break
+            q = next(j for j in range(3) if x[j] > 0)
+            x[q] -= 1
+            if spare > 0 and x[q] > 0:
+                x[q] -= 1
+                spare -= 1
+        s = [x for x in s if sum(x) > 0]
+    return rounds
+if Bn % 64 == 0:
+    now_w, now_b, pool_w, pool_b, blk_items, wav_items = [], [], [], [], [], []
+    for t in range(S):
+        ls = lane_slots(rec[t]).reshape(Bn // 16, 64, NS, 3)  # (waves, lanes, NSUB, 3)
+        wi = ls.sum((1, 3))  # (waves, NSUB) items per wave and substep
+        bi = wi.reshape(-1, 4, NS).sum(1)  # (blocks, NSUB)
+        r_now = np.array([[wave_rounds(ls[w, :, n]) if wi[w, n] else 0 for n in range(NS)] for w in range(ls.shape[0])])
+        R = -(-bi // 8)  # (blocks, NSUB) pooled rounds
+        r_pool = np.zeros_like(r_now)
+        for w in range(4):
+            first = (w + np.arange(NS)) % 4
+            r_pool[w::4] = np.maximum(0, -(-(R - first[None, :]) // 4))
+        now_w.append(r_now.sum(1)); pool_w.append(r_pool.sum(1))
+        now_b.append(r_now.sum(1).reshape(-1, 4).sum(1)); pool_b.append(R.sum(1))
+        blk_items.append(bi); wav_items.append(wi)
+    now_w, pool_w, now_b, pool_b = map(np.stack, (now_w, pool_w, now_b, pool_b))
+    bi, wi = np.concatenate(blk_items).ravel(), np.concatenate(wav_items).ravel()
+    print(f"four-lane: items per wave and collide substep mean {wi.mean():.1f} p90 {np.percentile(wi, 90):.0f} max {wi.max()}; "
+          f"substeps with an item {100 * (wi > 0).mean():.0f} %")
+    print(f"four-lane: items per block and collide substep median {np.median(bi):.0f} p90 {np.percentile(bi, 90):.0f} "
+          f"p99.9 {np.percentile(bi, 99.9):.0f} max {bi.max()}; largest substep of a block's step: median "
+          f"{np.median(np.concatenate(blk_items).max(1)):.0f}")
+    print(f"four-lane per-wave walk: rounds per wave per step mean {now_w.mean():.2f} p99 {np.percentile(now_w, 99):.0f} "
+          f"max {now_w.max()}, slowest wave per step {now_w.max(1).mean():.2f}, per block {now_b.mean():.2f}")
+    print(f"four-lane pooled walk:   rounds per wave per step mean {pool_w.mean():.2f}, slowest wave per step "
+          f"{pool_w.max(1).mean():.2f}, per block {pool_b.mean():.2f} ({100 * (pool_b.mean() / now_b.mean() - 1):+.0f} %)")
