@@ -107,3 +107,13 @@ POB_BW_D void bw_apply_range(const int base, const int n, const bool ovf, int &c
   c0 = 2 * base;
   c1 = ovf ? c0 : 2 * (base + n);
 }
+// the same range cut by body: a lane publishes its items slot by slot (bw_next_item), so the
+// contact slots of body l's n_l items are [c[l], c[l + 1]), c[0] = c0 and c[3] = c1 of
+// bw_apply_range (n = n0 + n1 + n2: a count that saturates overflows its wave) -- all four
+// equal in an overflowing block
+POB_BW_D void bw_body_ranges(const int base, const int n0, const int n1, const int n2, const bool ovf, int (&c)[4]) {
+  c[0] = 2 * base;
+  c[1] = ovf ? c[0] : c[0] + 2 * n0;
+  c[2] = ovf ? c[0] : c[1] + 2 * n1;
+  c[3] = ovf ? c[0] : c[2] + 2 * n2;
+}

@@ -180,7 +180,7 @@ struct QWalls {
   int nct;                // wall contacts of the position pass
   float c[6 * QK];        // the first QK: body, tau, n, dist (the re-walk builds, OVF)
   float seg[6 * QNB];     // nct > QK only: the segments a, b of the three bodies
-  int c0, c1;             // the block-cooperative walk only: the lane's contact slots [c0, c1)
+  int cb[QNB + 1];        // the block-cooperative walk only: body l's contact slots [cb[l], cb[l + 1]) (bw_body_ranges)
 };
 #ifndef POB_QUAD_WAVE_WALK
 #define POB_QUAD_WAVE_WALK 1  // 1: the wave-cooperative face walk (pob_mesh.h mesh_wave_walk)
@@ -535,6 +535,10 @@ POB_D void qwalls_detect(csys_t *Sp, const float *LT, const float *WT, const QBo
 //   its wave's segment; BARRIER 1; 3. evaluate: each wave its share of the block's rounds, the
 //   winners writing the contact slots; BARRIER 2; 4. apply: the owners read their slots in walk
 //   order in the position and the velocity pass (qcontacts_position / _velocity, COOP).
+// Publish and apply run body by body: a lane's walk order is "slot, then bit", so its records
+// and contact slots are grouped torso, Aux, lower leg (bw_body_ranges), and a loop per body with
+// the body a compile-time value needs no selects over the lane's three bodies (DESIGN.md §4
+// "Round-8 findings").
 // Two barriers per collide substep suffice: between barrier 2 and the next barrier 1 a wave
 // reads (apply) and writes (the next publish) only its OWN segment, and the others touch that
 // segment only between a barrier 1 and the barrier 2 after it (evaluation: they read its
@@ -562,38 +566,50 @@ POB_D void qwalls_detect_block(csys_t *Sp, const float *LT, const float *WT, con
                                QBlock &blk) {
   csys_t &S = *launder(Sp);
   uint64_t M[QNB];
+  QMesh ms;  // (the cull's segments: the publish writes them into the records)
   {
     const v3 rv_leg = qrot_xy(qcap_end(S, LT, 2, 0), b.q[2]);
-    QMesh ms;
     qmesh_segments(S, LT, b, rv_leg, ms);
     const uint32_t lw = qwall_mask(S, b);
     qmesh_items(S, LT, WT, lw | (lw << 8) | (lw << 16), ms, M);
   }
   if (blk.dead) { M[0] = 0ull; M[1] = 0ull; M[2] = 0ull; }
-  // publish: the lanes' items in lane order, each lane's in walk order
+#ifdef POB_EXP_NO_WALK
+  // timing experiment only: broadphase, face cull and the barriers, no items.  (This and the two
+  // below change the states: time the first few steps from reset only -- ants that sink into the
+  // walls load the later steps with items, DESIGN.md §4 "Round-8 findings")
+  M[0] = 0ull; M[1] = 0ull; M[2] = 0ull;
+#endif
+  // publish: the lanes' items in lane order, each lane's in walk order (slot, then bit) -- body
+  // by body with the slot a compile-time value: the record is the cull's segment of that body
   float *own = L.pool();
   const int nl = bw_lane_count(M[0], M[1], M[2]);
+  int nb[QNB];
+#pragma unroll
+  for (int l = 0; l < QNB; ++l) nb[l] = __builtin_popcountll(M[l]);
   int base = 0, tot = 0;
 #pragma unroll
   for (int bit = 0; bit < QBW_PREFIX_BITS; ++bit) bw_prefix_step(__ballot(((nl >> bit) & 1) != 0), L.t, bit, base, tot);
   {
     int at = base;
+#pragma unroll
+    for (int l = 0; l < QNB; ++l) {
+      const float r = q_cap_r(S, LT, l);
+      uint64_t m = M[l];
 #pragma nounroll
-    for (int k = 0; k < QBW_LANE_MAX; ++k) {
-      int s, bit;
-      const bool has = bw_next_item(M, s, bit);
-      if (!__any(has)) break;
-      v3 A, B;
-      float r;
-      bool seg;
-      qpose_seg(S, LT, b, s, A, B, r, seg);
-      if (has && at < QBW_WCAP) {
-        float *o = own + bw_item_off(at);
-        const float meta = __int_as_float(bw_meta(bit, seg, s));
-        o[0] = A.x; o[1] = A.y; o[2] = A.z; o[3] = B.x; o[4] = B.y; o[5] = B.z; o[6] = r; o[7] = meta;
-        o[2 * QBW_CON_DW] = meta;
+      while (__any(m != 0ull)) {
+        const bool has = m != 0ull;
+        const int bit = has ? __builtin_ctzll(m) : 0;
+        m &= m - 1ull;
+        if (has && at < QBW_WCAP) {
+          float *o = own + bw_item_off(at);
+          const float meta = __int_as_float(bw_meta(bit, l != 0, l));
+          o[0] = ms.a[l].x; o[1] = ms.a[l].y; o[2] = ms.a[l].z; o[3] = ms.b[l].x; o[4] = ms.b[l].y; o[5] = ms.b[l].z;
+          o[6] = r; o[7] = meta;
+          o[2 * QBW_CON_DW] = meta;
+        }
+        at += has ? 1 : 0;
       }
-      ++at;
     }
   }
   if (L.t == 0) own[bw_count_off()] = __int_as_float(tot);
@@ -612,8 +628,15 @@ POB_D void qwalls_detect_block(csys_t *Sp, const float *LT, const float *WT, con
   }
   qblock_barrier();  // BARRIER 2: every contact slot of the deal is written
   ++blk.sub;
-  bw_apply_range(base, nl, d.ovf, ws.c0, ws.c1);
-  ws.nct = ws.c1 - ws.c0;
+  bw_body_ranges(base, nb[0], nb[1], nb[2], d.ovf, ws.cb);
+#ifdef POB_EXP_NO_APPLY
+  {  // timing experiment only: the walk runs, its contacts are not applied
+    int z = ws.cb[0];
+    asm volatile("" : "+v"(z));
+    ws.cb[1] = z; ws.cb[2] = z; ws.cb[3] = z;
+  }
+#endif
+  ws.nct = ws.cb[QNB] - ws.cb[0];
 }
 
 // The lane's next contact slot in [c, c1) that holds a contact (c1: none left).  The owners
@@ -754,25 +777,39 @@ POB_D void qcontacts_position(csys_t *Sp, const float *LT, const float *WT, QBod
   }
   if (!WALLS || !__any(ws.nct != 0)) return;
   POB_FENCE();
+  if constexpr (COOP) {
+    // the block-cooperative walk: the lane's contact slots in its wave's segment, in walk order
+    // -- body by body (bw_body_ranges), so every operand of a body's loop is a fixed register:
+    // the same terms onto the same accumulators in the same order as one loop over [cb[0], cb[3])
+    const float *sg = L.pool();
+#pragma unroll
+    for (int l = 0; l < QNB; ++l) {
+      const int c1 = ws.cb[l + 1];
+      if (!__any(ws.cb[l] < c1)) continue;
+      const v3 px = L.get3(l, QF_PX);
+      const q4 pq = L.get4(l, QF_PQ);
+      // (the capsule end rotated once per body: qseg_point's operands)
+      const v3 rv = l == 0 ? V(0.0f, 0.0f, 0.0f) : qrot_xy(qcap_end(S, LT, l, 0), b.q[l]);
+      const float r = q_cap_r(S, LT, l), im = q_inv_mass(S, LT, l);
+      int c = qblock_next_hit(sg, ws.cb[l], c1);
+#pragma unroll 1
+      while (__any(c < c1)) {
+        if (c < c1) {
+          const float *p = sg + bw_con_off(c);
+          const float tau = p[0], dist = p[4];
+          const v3 pe = l == 0 ? b.x[0] : vfma(rv, tau, b.x[l]);
+          owall_position(g, SC, r - dist, pe, V(p[1], p[2], p[3]), 1e-6f + dist, im, b.x[l], b.q[l], pq, px, DX[l], DA[l]);
+          ++c;
+        }
+        c = qblock_next_hit(sg, c, c1);
+      }
+    }
+    return;
+  }
   v3 px[QNB];
   q4 pq[QNB];
 #pragma unroll
   for (int l = 0; l < QNB; ++l) { px[l] = L.get3(l, QF_PX); pq[l] = L.get4(l, QF_PQ); }
-  if constexpr (COOP) {  // the block-cooperative walk: the lane's contact slots in its wave's segment, in walk order
-    const float *sg = L.pool();
-    int c = qblock_next_hit(sg, ws.c0, ws.c1);
-#pragma unroll 1
-    while (__any(c < ws.c1)) {
-      if (c < ws.c1) {
-        const float *p = sg + bw_con_off(c);
-        const int l = bw_meta_slot(__float_as_int(sg[bw_meta_off(c >> 1)]));
-        qwall_pos_one(g, S, SC, LT, b.x, b.q, px, pq, l, p[0], V(p[1], p[2], p[3]), p[4], DX, DA);
-        ++c;
-      }
-      c = qblock_next_hit(sg, c, ws.c1);
-    }
-    return;
-  }
 #if POB_QUAD_WAVE_WALK
   if (!OVF) {  // the fast pass: the lane's list in the wave's pool (a wave with an overflow runs the step again)
     const float *pool = L.pool();
@@ -851,17 +888,26 @@ POB_D void qcontacts_velocity(csys_t *Sp, const float *LT, const float *WT, QBod
 #endif
   POB_FENCE();
   if constexpr (COOP) {
-    const float *sg = L.pool();
-    int c = qblock_next_hit(sg, ws.c0, ws.c1);
+    const float *sg = L.pool();  // (body by body, as the position pass)
+#pragma unroll
+    for (int l = 0; l < QNB; ++l) {
+      const int c1 = ws.cb[l + 1];
+      if (!__any(ws.cb[l] < c1)) continue;
+      const v3 rv = l == 0 ? V(0.0f, 0.0f, 0.0f) : qrot_xy(qcap_end(S, LT, l, 0), b.q[l]);
+      const float r = q_cap_r(S, LT, l), im = q_inv_mass(S, LT, l);
+      int c = qblock_next_hit(sg, ws.cb[l], c1);
 #pragma unroll 1
-    while (__any(c < ws.c1)) {
-      if (c < ws.c1) {
-        const float *p = sg + bw_con_off(c);
-        const int l = bw_meta_slot(__float_as_int(sg[bw_meta_off(c >> 1)]));
-        qwall_vel_one(g, S, SC, LT, b.x, b.q, b.v, b.w, l, p[0], V(p[1], p[2], p[3]), p[4], dV, dW);
-        ++c;
+      while (__any(c < c1)) {
+        if (c < c1) {
+          const float *p = sg + bw_con_off(c);
+          const float tau = p[0], dist = p[4];
+          const v3 pe = l == 0 ? b.x[0] : vfma(rv, tau, b.x[l]);
+          ocontact_vel_pe(g, SC, false, r - dist, pe, V(p[1], p[2], p[3]), 1e-6f + dist, im, b.x[l], b.v[l], b.w[l], dV[l],
+                          dW[l]);
+          ++c;
+        }
+        c = qblock_next_hit(sg, c, c1);
       }
-      c = qblock_next_hit(sg, c, ws.c1);
     }
     return;
   }
