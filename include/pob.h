@@ -199,6 +199,40 @@ int pob_random_actions(uint32_t *key_io, int total, int first, int B, int A, flo
 /* out[b, k] = obs[b, idx[k]] */
 int pob_obs_gather(const float *obs, int B, int D, const int32_t *idx, int K, float *out, void *stream);
 
+/* ---- policy networks (additive to ABI v8): po_brax/training/networks.py:34-54 (MLP),
+ * :80-123 (make_model / make_models) at inference, and the tanh-normal actor of brax's PPO
+ * (NormalTanhDistribution [ext]).  One launch runs every layer on the f32 matrix cores; the
+ * results equal the plain-C restatement of csrc/pob_mlp.h bit for bit (DESIGN.md "Policy
+ * networks": summation order, scalar functions, the head's formulas).
+ *
+ * Parameters: `theta` is ONE flat device float32 buffer W_0, b_0, W_1, b_1, .. where W_i is
+ * row-major (sizes[i], sizes[i + 1]) -- flax Dense.kernel's (in, out) layout -- and b_i has
+ * sizes[i + 1] entries; pob_mlp_param_count gives its length.  It is read at launch time
+ * and never copied, so an in-place update is seen by an already captured graph.
+ * Limits: 1 .. 8 layers, every width (the input's too) in 1 .. 256, any B >= 1.
+ * activation: 0 relu, 1 swish, 2 tanh, applied after every layer but the last (after the last
+ * too with activate_final).  pob_mlp_create / pob_mlp_destroy never call the HIP runtime. */
+typedef struct pob_mlp pob_mlp;
+int pob_mlp_create(int n_layers, const int *sizes /* n_layers + 1, sizes[0] = input */, int activation,
+                   int activate_final, pob_mlp **out);
+void pob_mlp_destroy(pob_mlp *mlp);
+int pob_mlp_param_count(const pob_mlp *mlp, long long *n);
+/* y (B, sizes[n_layers]) = MLP(x (B, sizes[0])) */
+int pob_mlp_forward(const pob_mlp *mlp, int B, const float *x, const float *theta, float *y, void *stream);
+/* The actor: logits = MLP(obs) (B, 2 A); loc, s = its halves; scale = softplus(s) + 0.001;
+ * eps = sqrt(2) erfinv(u), u = uniform(split(key_io)[1], (total, A), -1, 1)[first + b, a] (this
+ * batch is rows [first, first + B) of a batch of `total` envs: a shard equals the slice);
+ * raw = loc + scale eps; action = tanh(raw) (B, A); logp (B) = sum_a [-eps^2 / 2 - log scale
+ * - log(2 pi) / 2 - 2 (log 2 - raw - softplus(-2 raw))], a ascending.  Then key_io <-
+ * split(key_io)[0] by a one-thread launch (as pob_random_actions).  deterministic = 1: action =
+ * tanh(loc), raw = loc, logp untouched, key_io neither read nor advanced (may be NULL).
+ * Optional outputs (NULL = skip): logp, raw (B, A), logits (B, 2 A), obs_copy (B, sizes[0]) --
+ * the observation rows written out again (a trajectory slot) from the tile already loaded.
+ * The last width must be even. */
+int pob_policy_act(const pob_mlp *mlp, int B, int total, int first, const float *obs, const float *theta,
+                   uint32_t *key_io, int deterministic, float *action, float *logp, float *raw, float *logits,
+                   float *obs_copy, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2840,6 +2840,8 @@ static int hip_check(hipError_t e, const char *what) {
   snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
   return POB_EHIP;
 }
+// the same for the library's other translation units (pob_mlp.hip)
+__attribute__((visibility("hidden"))) int pob_fail_msg(int code, const char *msg) { return fail(code, msg); }
 static inline dim3 grid_for(int n, int bs) { return dim3((unsigned)((n + bs - 1) / bs)); }
 
 // host-side launch helpers (kind / storage dispatch)

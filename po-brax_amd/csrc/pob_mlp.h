@@ -1,0 +1,237 @@
+// pob_mlp.h -- the scalar math and the plain-C restatement of the policy-network kernels
+// (pob_mlp.hip: k_mlp_forward, k_policy_act).  Compiled for the device by hipcc and, with
+// POB_MLP_HOST, for the host by g++ (tests/host/mlp_host.cpp); both with -ffp-contract=off.
+//
+// Every function is a fixed sequence of float32 +, *, fmaf, integer bit operations, and the
+// correctly rounded reciprocal and square root (pob_rcp / pob_sqrt of pob_math.h on the device,
+// 1.0f / x and sqrtf on the host: the same values).  No ocml, no libm, no tables in memory, so
+// host and device give the same bits and mlp_forward_ref / policy_act_ref below ARE the
+// specification of the kernels (DESIGN.md "Policy networks").
+//
+// Layer: y[j] = act(b[j] + sum_k x[k] W[k][j]), W row-major (in, out).  The accumulator starts
+// from the bias and takes one fmaf per input feature in the order mlp_kfeat gives: k-step s
+// (one v_mfma_f32_32x32x2_f32) adds lane half 0's feature, then lane half 1's, i.e. natural
+// order 0, 1, 2, ..  An odd input width is padded with one zero feature (x = 0, w = 0), whose
+// fmaf(0, 0, acc) the restatement spells too (it turns an accumulator of -0 into +0).
+#pragma once
+#include <stdint.h>
+#ifdef POB_MLP_HOST
+#include <math.h>
+#define POB_MLP_D static inline
+POB_MLP_D float mlp_rcp(float x) { return 1.0f / x; }
+POB_MLP_D float mlp_sqrt(float x) { return sqrtf(x); }
+POB_MLP_D uint32_t mlp_f2u(float x) { uint32_t u; __builtin_memcpy(&u, &x, 4); return u; }
+POB_MLP_D float mlp_u2f(uint32_t u) { float x; __builtin_memcpy(&x, &u, 4); return x; }
+#else
+#include "pob_math.h"
+#define POB_MLP_D __device__ __forceinline__
+POB_MLP_D float mlp_rcp(float x) { return pob_rcp(x); }
+POB_MLP_D float mlp_sqrt(float x) { return pob_sqrt(x); }
+POB_MLP_D uint32_t mlp_f2u(float x) { return __float_as_uint(x); }
+POB_MLP_D float mlp_u2f(uint32_t u) { return __uint_as_float(u); }
+#endif
+#define MLP_FMA(a, b, c) __builtin_fmaf((a), (b), (c))
+
+#define POB_MLP_MAX_LAYERS 8
+#define POB_MLP_MAX_WIDTH 256
+enum { POB_ACT_RELU = 0, POB_ACT_SWISH = 1, POB_ACT_TANH = 2 };
+
+// input feature of k-step s, lane half h (the summation order: s ascending, h = 0 then 1)
+POB_MLP_D constexpr int mlp_kfeat(const int s, const int h) { return 2 * s + h; }
+POB_MLP_D constexpr int mlp_ksteps(const int in) { return (in + 1) >> 1; }
+
+// exp(x): n = rint(x log2 e) by the 1.5 * 2^23 shift, r = x - n ln 2 in two fused steps
+// (Cody-Waite), the degree-7 Taylor polynomial in Horner form, and the scale 2^n applied as
+// two exact powers of two, so results in the subnormal range round once.  x <= -104 gives 0,
+// x >= 89 gives inf, NaN gives NaN.
+POB_MLP_D float pob_expf(float x) {
+  x = x < -104.0f ? -104.0f : x;
+  x = x > 89.0f ? 89.0f : x;
+  const float t = MLP_FMA(x, 1.44269504f, 12582912.0f);
+  const float fn = t - 12582912.0f;
+  const int n = (int)(mlp_f2u(t) - 0x4B400000u);
+  float r = MLP_FMA(fn, -0.693145751953125f, x);
+  r = MLP_FMA(fn, -1.42860677e-6f, r);
+  float p = 1.98412698e-4f;
+  p = MLP_FMA(p, r, 1.38888889e-3f);
+  p = MLP_FMA(p, r, 8.33333333e-3f);
+  p = MLP_FMA(p, r, 4.16666667e-2f);
+  p = MLP_FMA(p, r, 1.66666667e-1f);
+  p = MLP_FMA(p, r, 0.5f);
+  p = MLP_FMA(p, r, 1.0f);
+  p = MLP_FMA(p, r, 1.0f);
+  const int n1 = n >> 1, n2 = n - n1;
+  const float s1 = mlp_u2f((uint32_t)(n1 + 127) << 23), s2 = mlp_u2f((uint32_t)(n2 + 127) << 23);
+  return (p * s1) * s2;
+}
+
+// log(x): x = 2^k m with m in [sqrt(1/2), sqrt(2)), f = m - 1 (exact), s = f / (2 + f),
+// log m = f - (f^2/2 - s (f^2/2 + R(s^2))) with the four-term even polynomial of the fdlibm
+// family [ext], then k ln 2 in two parts.  Subnormal x is scaled by 2^25 first.  log(0) =
+// -inf, x < 0 and NaN give NaN, inf gives inf.
+POB_MLP_D float pob_logf(float x) {
+  const bool sub = x < 0x1p-126f;
+  const float xs = sub ? x * 0x1p25f : x;
+  uint32_t ix = mlp_f2u(xs) + (0x3F800000u - 0x3F3504F3u);
+  const int k = (int)(ix >> 23) - 127 - (sub ? 25 : 0);
+  ix = (ix & 0x007FFFFFu) + 0x3F3504F3u;
+  const float f = mlp_u2f(ix) - 1.0f;
+  const float s = f * mlp_rcp(2.0f + f);
+  const float z = s * s, w = z * z;
+  const float t1 = w * MLP_FMA(w, 0.24279078841f, 0.40000972152f);
+  const float t2 = z * MLP_FMA(w, 0.28498786688f, 0.66666662693f);
+  const float R = t2 + t1;
+  const float hfsq = (0.5f * f) * f;
+  const float dk = (float)k;
+  float r = MLP_FMA(s, hfsq + R, dk * 9.0580006145e-06f);
+  r = ((r - hfsq) + f) + dk * 6.9313812256e-01f;
+  r = x == 0.0f ? mlp_u2f(0xFF800000u) : r;
+  r = x < 0.0f ? mlp_u2f(0x7FC00000u) : r;
+  r = mlp_f2u(x) == 0x7F800000u ? x : r;
+  r = x != x ? x : r;
+  return r;
+}
+
+// tanh(x): |x| < 0.625 the odd polynomial x + x z P(z), z = x^2 (Cephes form [ext]); else
+// 1 - 2 / (exp(2 |x|) + 1) with the sign of x; |x| >= 10 gives +-1.
+POB_MLP_D float pob_tanhf(float x) {
+  const float a = x < 0.0f ? -x : x;
+  const float z = x * x;
+  float p = -5.70498872745e-3f;
+  p = MLP_FMA(p, z, 2.06390887954e-2f);
+  p = MLP_FMA(p, z, -5.37397155531e-2f);
+  p = MLP_FMA(p, z, 1.33314422036e-1f);
+  p = MLP_FMA(p, z, -3.33332819422e-1f);
+  const float small = MLP_FMA(p * z, x, x);
+  const float e = pob_expf(2.0f * (a > 10.0f ? 10.0f : a));
+  float big = 1.0f - 2.0f * mlp_rcp(e + 1.0f);
+  big = x < 0.0f ? -big : big;
+  float r = a < 0.625f ? small : big;
+  r = x != x ? x : r;
+  return r;
+}
+
+// log1p(t) for t in [0, 1]: u = fl(1 + t), log u + (t - (u - 1)) / u (the rounding of 1 + t
+// given back to first order; t below 2^-24 returns t)
+POB_MLP_D float pob_log1p_unit(float t) {
+  const float u = 1.0f + t;
+  const float c = t - (u - 1.0f);
+  return MLP_FMA(c, mlp_rcp(u), pob_logf(u));
+}
+// softplus(x) = max(x, 0) + log1p(exp(-|x|)): no cancellation on either side
+POB_MLP_D float pob_softplusf(float x) {
+  const float a = x < 0.0f ? -x : x;
+  const float m = x > 0.0f ? x : 0.0f;
+  const float r = m + pob_log1p_unit(pob_expf(-a));
+  return x != x ? x : r;
+}
+// sigmoid(x) = 1 / (1 + exp(-x)); swish(x) = x sigmoid(x)
+POB_MLP_D float pob_sigmoidf(float x) { return mlp_rcp(1.0f + pob_expf(-x)); }
+POB_MLP_D float pob_swishf(float x) { return x * pob_sigmoidf(x); }
+
+// erfinv(x) on (-1, 1): w = -log((1 - x)(1 + x)); two polynomials, in w - 2.5 for w < 5 and in
+// sqrt(w) - 3 beyond (M. Giles, "Approximating the erfinv function", 2010 [ext]), times x.
+POB_MLP_D float pob_erfinvf(float x) {
+  const float w = -pob_logf((1.0f - x) * (1.0f + x));
+  const float wc = w - 2.5f;
+  float p = 2.81022636e-08f;
+  p = MLP_FMA(p, wc, 3.43273939e-07f);
+  p = MLP_FMA(p, wc, -3.5233877e-06f);
+  p = MLP_FMA(p, wc, -4.39150654e-06f);
+  p = MLP_FMA(p, wc, 0.00021858087f);
+  p = MLP_FMA(p, wc, -0.00125372503f);
+  p = MLP_FMA(p, wc, -0.00417768164f);
+  p = MLP_FMA(p, wc, 0.246640727f);
+  p = MLP_FMA(p, wc, 1.50140941f);
+  const float wt = mlp_sqrt(w < 5.0f ? 5.0f : w) - 3.0f;
+  float q = -0.000200214257f;
+  q = MLP_FMA(q, wt, 0.000100950558f);
+  q = MLP_FMA(q, wt, 0.00134934322f);
+  q = MLP_FMA(q, wt, -0.00367342844f);
+  q = MLP_FMA(q, wt, 0.00573950773f);
+  q = MLP_FMA(q, wt, -0.0076224613f);
+  q = MLP_FMA(q, wt, 0.00943887047f);
+  q = MLP_FMA(q, wt, 1.00167406f);
+  q = MLP_FMA(q, wt, 2.83297682f);
+  return (w < 5.0f ? p : q) * x;
+}
+
+POB_MLP_D float mlp_activate(const int act, const float x) {
+  if (act == POB_ACT_RELU) return x > 0.0f ? x : 0.0f;
+  if (act == POB_ACT_SWISH) return pob_swishf(x);
+  return pob_tanhf(x);
+}
+
+// The tanh-normal head of one action component (brax NormalTanhDistribution [ext]): scale =
+// softplus(s) + 0.001, eps = sqrt(2) erfinv(u) with u clamped to -1 + 2^-24 from below (the
+// uniform draw can return -1), raw = loc + scale eps, action = tanh(raw), and the component's
+// log-probability term -eps^2/2 - log scale - log(2 pi)/2 - 2 (log 2 - raw - softplus(-2 raw)).
+#define POB_U_MIN (-0x1.fffffep-1f)
+POB_MLP_D void pob_tanh_normal(const float loc, const float s, float u, float &action, float &raw, float &term) {
+  const float scale = pob_softplusf(s) + 0.001f;
+  u = u > POB_U_MIN ? u : POB_U_MIN;
+  const float eps = 1.41421354f * pob_erfinvf(u);
+  raw = MLP_FMA(scale, eps, loc);
+  action = pob_tanhf(raw);
+  const float t0 = (-0.5f * eps) * eps;
+  const float t1 = (t0 - pob_logf(scale)) - 0.918938533f;
+  const float ld = 2.0f * ((0.693147181f - raw) - pob_softplusf(-2.0f * raw));
+  term = t1 - ld;
+}
+
+#ifdef POB_MLP_HOST
+// ---------------------------------------------------------------------------- restatement
+// theta packing: W_0 (in_0, out_0) row-major, b_0 (out_0), W_1, b_1, ..  (sizes[0] = input)
+static inline long long mlp_param_count(const int n_layers, const int *sizes) {
+  long long n = 0;
+  for (int l = 0; l < n_layers; ++l) n += ((long long)sizes[l] + 1) * sizes[l + 1];
+  return n;
+}
+// y (B, sizes[n_layers]) = the network on x (B, sizes[0])
+static inline void mlp_forward_ref(const int n_layers, const int *sizes, const int activation, const int activate_final,
+                                   const int B, const float *x, const float *theta, float *y) {
+  float a[POB_MLP_MAX_WIDTH + 1], o[POB_MLP_MAX_WIDTH + 1];
+  for (int b = 0; b < B; ++b) {
+    for (int k = 0; k < sizes[0]; ++k) a[k] = x[(long long)b * sizes[0] + k];
+    const float *W = theta;
+    for (int l = 0; l < n_layers; ++l) {
+      const int in = sizes[l], out = sizes[l + 1];
+      const float *bias = W + (long long)in * out;
+      for (int j = 0; j < out; ++j) {
+        float acc = bias[j];
+        for (int s = 0; s < mlp_ksteps(in); ++s)
+          for (int h = 0; h < 2; ++h) {
+            const int k = mlp_kfeat(s, h);
+            acc = k < in ? MLP_FMA(W[(long long)k * out + j], a[k], acc) : MLP_FMA(0.0f, 0.0f, acc);
+          }
+        o[j] = (l != n_layers - 1 || activate_final) ? mlp_activate(activation, acc) : acc;
+      }
+      for (int j = 0; j < out; ++j) a[j] = o[j];
+      W = bias + out;
+    }
+    for (int j = 0; j < sizes[n_layers]; ++j) y[(long long)b * sizes[n_layers] + j] = a[j];
+  }
+}
+// The actor on rows of logits (B, 2 A) and the uniform draws u (B, A); logp sums the terms in
+// natural order a = 0 .. A - 1 from +0.  Deterministic: action = tanh(loc), raw = loc, logp
+// is not written.
+static inline void policy_head_ref(const int B, const int A, const float *logits, const float *u, const int deterministic,
+                                   float *action, float *logp, float *raw) {
+  for (int b = 0; b < B; ++b) {
+    float sum = 0.0f;
+    for (int a = 0; a < A; ++a) {
+      const float loc = logits[(long long)b * 2 * A + a], s = logits[(long long)b * 2 * A + A + a];
+      float act, rw, term;
+      if (deterministic) {
+        act = pob_tanhf(loc); rw = loc;
+      } else {
+        pob_tanh_normal(loc, s, u[(long long)b * A + a], act, rw, term);
+        sum = sum + term;
+      }
+      action[(long long)b * A + a] = act;
+      raw[(long long)b * A + a] = rw;
+    }
+    if (!deterministic) logp[b] = sum;
+  }
+}
+#endif

@@ -1,0 +1,308 @@
+// pob_mlp.hip -- policy networks on the matrix cores (gfx950): the fused MLP forward and the
+// tanh-normal actor of DESIGN.md "Policy networks".
+//
+//   k_mlp_forward   y = MLP(x): every layer in one launch
+//   k_policy_act    the same forward, then the tanh-normal head (brax NormalTanhDistribution [ext])
+//
+// One 64-lane block (one wave) owns a tile of 32 batch rows.  It computes Y^T = W^T X^T with
+// v_mfma_f32_32x32x2_f32: the env is the C column (lane & 31), the A operand of k-step s is row
+// k = mlp_kfeat(s, lane >> 5) of W read from the caller's parameter buffer (coalesced, L2
+// resident, never copied: an optimiser's in-place update is seen by a captured graph), the B
+// operand is the activation of that feature from LDS.  The instruction is bit for bit
+// fma(a_k1, b_k1, fma(a_k0, b_k0, C)), so with the accumulator started from the bias the layer
+// is the fmaf chain of pob_mlp.h mlp_forward_ref, and the activations are that header's scalar
+// functions: the kernels equal the restatement exactly.
+//
+// Activations live in two LDS images [feature][env] (pitch 33 floats: conflict-free both for the
+// row-major global <-> LDS copies, where consecutive lanes walk features, and for the operand
+// reads, where they walk envs), layer l reading image l & 1 and writing the other.  Both lie
+// in one static pool whose height is a template parameter (64 / 152 / 288 / 512 features in
+// all), chosen per network at launch, the second image starting behind the first one's widest
+// layer: the reference's policy network takes 152 rows = 20 064 B, eight blocks per CU.  The
+// first image is staged from 32 contiguous observation rows with coalesced loads, sixteen in
+// flight per lane (tail rows clamped), outputs leave through the same images with coalesced
+// stores (tail rows masked).
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cstdio>
+#include <new>
+
+#include "../../include/pob.h"
+#include "pob_mlp.h"
+
+// sets pob_last_error's thread-local message (pob_kernels.hip)
+int pob_fail_msg(int code, const char *msg);
+
+#define MLP_ROWS 32    // batch rows of a tile
+#define MLP_PITCH 33   // floats between two features of an LDS image
+#define MLP_KUNROLL 16 // k-steps whose operands are loaded ahead of their MFMAs
+#define MLP_STAGE 16   // observation elements a lane loads ahead of their LDS stores
+
+typedef float mlp_f32x16 __attribute__((ext_vector_type(16)));
+
+struct MlpDesc {
+  int n_layers;
+  int sizes[POB_MLP_MAX_LAYERS + 1];
+  int act, act_final;
+};
+
+// register r of lane half h holds output feature (r & 3) + 8 (r >> 2) + 4 h of the 32-feature tile
+POB_MLP_D int mlp_acc_row(const int r, const int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+// one layer: src image (in features) -> dst image (out features)
+POB_MLP_D void mlp_layer(const float *src, float *dst, const float *W, const float *bias, const int in, const int out,
+                         const bool activate, const int act, const int lane) {
+  const int j = lane & 31, h = lane >> 5;
+  const int ks = mlp_ksteps(in);
+  for (int ot = 0; ot < out; ot += 32) {
+    mlp_f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int i = ot + mlp_acc_row(r, h);
+      acc[r] = i < out ? bias[i] : 0.0f;
+    }
+    const int col = ot + j;  // this lane's row of W^T
+    const bool cok = col < out;
+    for (int s0 = 0; s0 < ks; s0 += MLP_KUNROLL) {
+      float a[MLP_KUNROLL], b[MLP_KUNROLL];
+#pragma unroll
+      for (int u = 0; u < MLP_KUNROLL; ++u) {
+        const int k = mlp_kfeat(s0 + u, h);
+        const bool kok = k < in;
+        a[u] = (kok && cok) ? W[(size_t)k * out + col] : 0.0f;
+        b[u] = kok ? src[k * MLP_PITCH + j] : 0.0f;
+      }
+#pragma unroll
+      for (int u = 0; u < MLP_KUNROLL; ++u)
+        if (s0 + u < ks) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b[u], acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int i = ot + mlp_acc_row(r, h);
+      if (i < out) dst[i * MLP_PITCH + j] = activate ? mlp_activate(act, acc[r]) : acc[r];
+    }
+  }
+}
+
+// rows [b0, b0 + valid) of a row-major (B, width) array <- features [f0, f0 + width) of an image
+POB_MLP_D void mlp_tile_store(float *dst, const float *img, const int f0, const int width, const int b0, const int valid,
+                              const int lane) {
+  float *d = dst + (size_t)b0 * width;
+  for (int e = lane; e < MLP_ROWS * width; e += 64) {
+    const int row = e / width, col = e - row * width;
+    if (row < valid) d[e] = img[(f0 + col) * MLP_PITCH + row];
+  }
+}
+
+// The forward of one tile.  Returns the image holding the last layer's output.
+POB_MLP_D float *mlp_tile_forward(const MlpDesc &d, float *imgA, float *imgB, const int B, const int b0, const float *x,
+                                  const float *theta, float *obs_copy, const int lane) {
+  const int D = d.sizes[0];
+  const int valid = B - b0 < MLP_ROWS ? B - b0 : MLP_ROWS;
+  // element e = row D + col of the tile's 32 contiguous rows; a lane's elements are 64 apart
+  const int dq = 64 / D, dr = 64 - dq * D;
+  int row = lane / D, col = lane - row * D;
+  for (int e0 = lane; e0 < MLP_ROWS * D; e0 += 64 * MLP_STAGE) {
+    float v[MLP_STAGE];
+    int at[MLP_STAGE];  // the element's place in the image (-1: past the tile), bit 30: a row to copy out
+#pragma unroll
+    for (int u = 0; u < MLP_STAGE; ++u) {
+      const bool in_tile = e0 + 64 * u < MLP_ROWS * D;
+      const int rr = row < valid ? row : valid - 1;  // tail rows repeat the last one
+      v[u] = in_tile ? x[(size_t)(b0 + rr) * D + col] : 0.0f;
+      at[u] = in_tile ? (col * MLP_PITCH + row) | (row < valid ? 1 << 30 : 0) : -1;
+      row += dq; col += dr;
+      if (col >= D) { col -= D; ++row; }
+    }
+#pragma unroll
+    for (int u = 0; u < MLP_STAGE; ++u) {
+      if (at[u] >= 0) {
+        imgA[at[u] & 0xFFFFF] = v[u];
+        if (obs_copy && (at[u] >> 30)) obs_copy[(size_t)b0 * D + e0 + 64 * u] = v[u];
+      }
+    }
+  }
+  __syncthreads();
+  float *src = imgA, *dst = imgB;
+  const float *W = theta;
+  for (int l = 0; l < d.n_layers; ++l) {
+    const int in = d.sizes[l], out = d.sizes[l + 1];
+    const float *bias = W + (size_t)in * out;
+    mlp_layer(src, dst, W, bias, in, out, l != d.n_layers - 1 || d.act_final, d.act, lane);
+    __syncthreads();
+    W = bias + out;
+    float *t = src; src = dst; dst = t;
+  }
+  return src;
+}
+
+template <int H>
+__global__ __launch_bounds__(64) void k_mlp_forward(const MlpDesc d, const int split, const int B, const float *x,
+                                                    const float *theta, float *y) {
+  __shared__ float img[H * MLP_PITCH];
+  float *imgA = img, *imgB = img + split * MLP_PITCH;
+  const int lane = threadIdx.x, b0 = blockIdx.x * MLP_ROWS;
+  const float *out = mlp_tile_forward(d, imgA, imgB, B, b0, x, theta, nullptr, lane);
+  const int valid = B - b0 < MLP_ROWS ? B - b0 : MLP_ROWS;
+  mlp_tile_store(y, out, 0, d.sizes[d.n_layers], b0, valid, lane);
+}
+
+// Env b of this launch is env first + b of a batch of `total`: its draw for action component a
+// is element (first + b) A + a of uniform(split(key)[1], (total, A), -1, 1).  The key is only
+// read here (k_mlp_advance_key, launched after, advances it).
+template <int H>
+__global__ __launch_bounds__(64) void k_policy_act(const MlpDesc d, const int split, const int B, const int total,
+                                                   const int first, const float *obs, const float *theta,
+                                                   const uint32_t *key, const int deterministic, float *action,
+                                                   float *logp, float *raw, float *logits, float *obs_copy) {
+  __shared__ float img[H * MLP_PITCH];
+  float *imgA = img, *imgB = img + split * MLP_PITCH;
+  const int lane = threadIdx.x, b0 = blockIdx.x * MLP_ROWS;
+  float *L = mlp_tile_forward(d, imgA, imgB, B, b0, obs, theta, obs_copy, lane);
+  float *T = L == imgA ? imgB : imgA;  // the per-component log-probability terms
+  const int valid = B - b0 < MLP_ROWS ? B - b0 : MLP_ROWS;
+  const int A = d.sizes[d.n_layers] >> 1;
+  if (logits) {
+    mlp_tile_store(logits, L, 0, 2 * A, b0, valid, lane);
+    __syncthreads();
+  }
+  uint32_t s0 = 0u, s1 = 0u;
+  if (!deterministic) tf_split(key[0], key[1], 2u, 1u, s0, s1);
+  for (int e = lane; e < MLP_ROWS * A; e += 64) {
+    const int env = e & 31, a = e >> 5;
+    if (env >= valid) continue;
+    const float loc = L[a * MLP_PITCH + env], s = L[(A + a) * MLP_PITCH + env];
+    float act, rw;
+    if (deterministic) {
+      act = pob_tanhf(loc);
+      rw = loc;
+    } else {
+      const uint32_t i = (uint32_t)(first + b0 + env) * (uint32_t)A + (uint32_t)a;
+      const float u = tf_uniform(s0, s1, (uint32_t)total * (uint32_t)A, i, -1.0f, 1.0f);
+      float term;
+      pob_tanh_normal(loc, s, u, act, rw, term);
+      T[a * MLP_PITCH + env] = term;
+    }
+    L[a * MLP_PITCH + env] = act;
+    L[(A + a) * MLP_PITCH + env] = rw;
+  }
+  __syncthreads();
+  mlp_tile_store(action, L, 0, A, b0, valid, lane);
+  if (raw) mlp_tile_store(raw, L, A, A, b0, valid, lane);
+  if (!deterministic && logp && lane < valid) {
+    float sum = 0.0f;
+    for (int a = 0; a < A; ++a) sum = sum + T[a * MLP_PITCH + lane];
+    logp[b0 + lane] = sum;
+  }
+}
+
+__global__ void k_mlp_advance_key(uint32_t *key) {
+  uint32_t o0, o1;
+  tf_split(key[0], key[1], 2u, 0u, o0, o1);
+  key[0] = o0; key[1] = o1;
+}
+
+// ============================================================================ C ABI
+struct pob_mlp {
+  MlpDesc d;
+  long long n_params;
+};
+
+// The two images' heights: image l & 1 holds sizes[l]; the actor's terms (A features) go to the
+// image the logits are not in.  Image B starts at row `split` of the pool; returns the pool's
+// height class (0 .. 3: 64 / 152 / 288 / 512 rows).
+static int image_rows(const MlpDesc &d, bool head, int &split) {
+  int w[2] = {1, 1};
+  for (int l = 0; l <= d.n_layers; ++l)
+    if (d.sizes[l] > w[l & 1]) w[l & 1] = d.sizes[l];
+  if (head) {
+    const int A = d.sizes[d.n_layers] >> 1, o = (d.n_layers + 1) & 1;
+    if (A > w[o]) w[o] = A;
+  }
+  split = w[0];
+  const int rows = w[0] + w[1];
+  return rows <= 64 ? 0 : (rows <= 152 ? 1 : (rows <= 288 ? 2 : 3));
+}
+
+#define MLP_DISPATCH(KERNEL, cls, ...)                                                      \
+  switch (cls) {                                                                            \
+    case 0: hipLaunchKernelGGL((KERNEL<64>), grid, dim3(64), 0, st, __VA_ARGS__); break;    \
+    case 1: hipLaunchKernelGGL((KERNEL<152>), grid, dim3(64), 0, st, __VA_ARGS__); break;   \
+    case 2: hipLaunchKernelGGL((KERNEL<288>), grid, dim3(64), 0, st, __VA_ARGS__); break;   \
+    default: hipLaunchKernelGGL((KERNEL<512>), grid, dim3(64), 0, st, __VA_ARGS__); break;  \
+  }
+
+static int mlp_hip_check(hipError_t e, const char *what) {
+  if (e == hipSuccess) return POB_OK;
+  char msg[256];
+  snprintf(msg, sizeof(msg), "%s: %s", what, hipGetErrorString(e));
+  return pob_fail_msg(POB_EHIP, msg);
+}
+
+extern "C" {
+
+int pob_mlp_create(int n_layers, const int *sizes, int activation, int activate_final, pob_mlp **out) {
+  if (!out) return pob_fail_msg(POB_EINVAL, "mlp: out is NULL");
+  *out = nullptr;
+  if (!sizes) return pob_fail_msg(POB_EINVAL, "mlp: sizes is NULL");
+  if (n_layers < 1 || n_layers > POB_MLP_MAX_LAYERS) return pob_fail_msg(POB_EINVAL, "mlp: 1 to 8 layers");
+  for (int l = 0; l <= n_layers; ++l)
+    if (sizes[l] < 1 || sizes[l] > POB_MLP_MAX_WIDTH) return pob_fail_msg(POB_EINVAL, "mlp: every width must be in 1 .. 256");
+  if (activation != POB_ACT_RELU && activation != POB_ACT_SWISH && activation != POB_ACT_TANH)
+    return pob_fail_msg(POB_EINVAL, "mlp: unknown activation (0 relu, 1 swish, 2 tanh)");
+  pob_mlp *m = new (std::nothrow) pob_mlp();
+  if (!m) return pob_fail_msg(POB_ENOMEM, "mlp: out of memory");
+  m->d.n_layers = n_layers;
+  m->n_params = 0;
+  for (int l = 0; l <= POB_MLP_MAX_LAYERS; ++l) m->d.sizes[l] = l <= n_layers ? sizes[l] : 0;
+  for (int l = 0; l < n_layers; ++l) m->n_params += ((long long)sizes[l] + 1) * sizes[l + 1];
+  m->d.act = activation;
+  m->d.act_final = activate_final ? 1 : 0;
+  *out = m;
+  return POB_OK;
+}
+
+void pob_mlp_destroy(pob_mlp *m) { delete m; }
+
+int pob_mlp_param_count(const pob_mlp *m, long long *n) {
+  if (!m || !n) return pob_fail_msg(POB_EINVAL, "mlp: NULL argument");
+  *n = m->n_params;
+  return POB_OK;
+}
+
+int pob_mlp_forward(const pob_mlp *m, int B, const float *x, const float *theta, float *y, void *stream) {
+  if (!m) return pob_fail_msg(POB_EINVAL, "mlp is NULL");
+  if (B < 1) return pob_fail_msg(POB_EINVAL, "mlp: batch size must be positive");
+  if (!x || !theta || !y) return pob_fail_msg(POB_EINVAL, "mlp: NULL argument");
+  int split;
+  const int cls = image_rows(m->d, false, split);
+  const dim3 grid((unsigned)((B + MLP_ROWS - 1) / MLP_ROWS));
+  hipStream_t st = (hipStream_t)stream;
+  MLP_DISPATCH(k_mlp_forward, cls, m->d, split, B, x, theta, y)
+  return mlp_hip_check(hipGetLastError(), "k_mlp_forward launch");
+}
+
+int pob_policy_act(const pob_mlp *m, int B, int total, int first, const float *obs, const float *theta,
+                   uint32_t *key_io, int deterministic, float *action, float *logp, float *raw, float *logits,
+                   float *obs_copy, void *stream) {
+  if (!m) return pob_fail_msg(POB_EINVAL, "mlp is NULL");
+  const int out = m->d.sizes[m->d.n_layers];
+  if (out & 1) return pob_fail_msg(POB_EINVAL, "policy: the last width must be even (loc and scale halves)");
+  if (B < 1 || first < 0 || total < 1 || (long long)first + B > total)
+    return pob_fail_msg(POB_EINVAL, "policy: bad shard (need first >= 0, B >= 1, first + B <= total)");
+  if ((long long)total * (out >> 1) >= 4294967295LL) return pob_fail_msg(POB_EINVAL, "policy: too many action elements");
+  if (!obs || !theta || !action) return pob_fail_msg(POB_EINVAL, "policy: NULL argument");
+  if (!deterministic && !key_io) return pob_fail_msg(POB_EINVAL, "policy: key is NULL");
+  int split;
+  const int cls = image_rows(m->d, true, split);
+  const dim3 grid((unsigned)((B + MLP_ROWS - 1) / MLP_ROWS));
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t *key = key_io;
+  MLP_DISPATCH(k_policy_act, cls, m->d, split, B, total, first, obs, theta, key, deterministic, action, logp, raw, logits,
+               obs_copy)
+  if (!deterministic) hipLaunchKernelGGL(k_mlp_advance_key, dim3(1), dim3(1), 0, st, key_io);
+  return mlp_hip_check(hipGetLastError(), "k_policy_act launch");
+}
+
+}  // extern "C"

@@ -261,3 +261,58 @@ class PolicyRollout:
         """Run the captured unroll (stream-ordered on torch's current stream)."""
         self.graph.replay()
         return self.state
+
+
+class ActorRollout:
+    """The native unroll of a ``training.networks.NormalTanhPolicy``: ``T`` env-steps captured
+    into ONE hipGraph, per step one ``pob_policy_act`` launch (forward, tanh-normal head, and
+    the observation rows written out again) straight into the (T, B, ...) trajectory buffers,
+    the one-thread key advance, the fused step kernel, and the reward / done copies.  Equal,
+    bit for bit, to ``PolicyRollout`` with the same policy, without its per-step observation
+    and action copies.
+
+        roll = ActorRollout(env, state, policy, steps=T)
+        roll.replay()
+        roll.obs[t], roll.actions[t], roll.logp[t], roll.raw[t]   # what the policy saw and did
+        roll.reward[t], roll.done[t]                              # the step's outcome
+
+    The parameters are read at replay time: ``policy.theta`` updated in place between replays
+    changes the next replay's actions.  Single-kind ``create(...)`` chains only."""
+
+    def __init__(self, env, state, policy, steps: int):
+        from .training.networks import NormalTanhPolicy
+        if steps <= 0:
+            raise ValueError("steps must be positive")
+        if not isinstance(policy, NormalTanhPolicy):
+            raise TypeError("policy must be a training.networks.NormalTanhPolicy")
+        if isinstance(state, (list, tuple)):
+            raise NotImplementedError("ActorRollout unrolls a single-kind create(...) env, not a MixedEnv")
+        obs = state.obs
+        if not (obs.is_cuda and obs.dtype == torch.float32 and obs.dim() == 2):
+            raise ValueError("state.obs must be a float32 (B, D) device tensor")
+        B, D = int(obs.shape[0]), int(obs.shape[1])
+        A = env.action_size
+        if policy.action_size != A or policy.obs_size != D:
+            raise ValueError(f"the policy maps {policy.obs_size} -> {policy.action_size}, the env {D} -> {A}")
+        self.env, self.state, self.policy, self.steps = env, state, policy, int(steps)
+        dev, T = obs.device, self.steps
+        self.obs = torch.empty((T, B, D), dtype=torch.float32, device=dev)
+        self.actions = torch.empty((T, B, A), dtype=torch.float32, device=dev)
+        self.raw = torch.empty((T, B, A), dtype=torch.float32, device=dev)
+        self.logp = torch.zeros((T, B), dtype=torch.float32, device=dev)
+        self.reward = torch.empty((T, B), dtype=torch.float32, device=dev)
+        self.done = torch.empty((T, B), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.graph = torch.cuda.CUDAGraph()
+        with no_gc(), torch.cuda.graph(self.graph):
+            for t in range(T):
+                policy.act_into(self.state.obs, self.actions[t], self.logp[t], self.raw[t], None, self.obs[t])
+                self.state = env.step_(self.state, self.actions[t])
+                self.reward[t].copy_(self.state.reward)
+                self.done[t].copy_(self.state.aux["done"] if "done" in self.state.aux else self.state.done)
+        _release_deferred()
+
+    def replay(self):
+        """Run the captured unroll (stream-ordered on torch's current stream)."""
+        self.graph.replay()
+        return self.state

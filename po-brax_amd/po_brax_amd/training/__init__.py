@@ -1,0 +1,3 @@
+"""Learner-side pieces with a native inference path (po_brax/training in the reference)."""
+from . import networks  # noqa: F401
+from .networks import FeedForwardModel, NormalTanhPolicy, make_model, make_models  # noqa: F401

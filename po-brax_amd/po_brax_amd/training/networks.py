@@ -1,0 +1,270 @@
+"""Policy / value networks (po_brax/training/networks.py: MLP, make_model, make_models).
+
+The reference builds flax MLPs for the learner.  Here a model is a pair ``(init, apply)`` over
+ONE flat float32 parameter vector ``theta`` (W_0, b_0, W_1, b_1, ..; W_i row-major (in, out),
+flax ``Dense.kernel``'s layout), of which the ``{"hidden_i": {"kernel", "bias"}}`` mapping holds
+views.  ``apply`` runs the fused HIP kernel (``pob_mlp_forward``: every layer in one launch on
+the f32 matrix cores) when ``x`` is a CUDA float32 tensor and no gradient is required, and the
+same network in plain torch ops otherwise (autograd for the learner, and the CPU).
+``NormalTanhPolicy`` is the actor: forward + brax's tanh-normal head in one launch
+(``pob_policy_act``), capture-safe, so it drops into ``rollout.PolicyRollout`` and is what
+``rollout.ActorRollout`` unrolls.  Formulas, layouts and what is pinned: DESIGN.md "Policy
+networks".
+"""
+from __future__ import annotations
+
+import ctypes as C
+import dataclasses
+import math
+from typing import Any, Callable, Optional, Sequence, Tuple
+
+import torch
+
+from .. import _lib
+from .._lib import check, lib, ptr
+
+ACTIVATIONS = {"relu": 0, "swish": 1, "silu": 1, "tanh": 2}
+_TORCH_ACT = {0: torch.relu, 1: torch.nn.functional.silu, 2: torch.tanh}
+MAX_LAYERS, MAX_WIDTH = 8, 256
+
+
+def _activation_id(activation) -> int:
+    if isinstance(activation, str):
+        name = activation
+    else:
+        name = getattr(activation, "__name__", str(activation))
+    if name not in ACTIVATIONS:
+        raise ValueError(f"activation must be one of {sorted(ACTIVATIONS)}, got {activation!r}")
+    return ACTIVATIONS[name]
+
+
+class MLPHandle:
+    """A ``pob_mlp`` (shape and activation only: host memory, no HIP call to make or free)."""
+
+    def __init__(self, sizes: Sequence[int], activation: int, activate_final: bool = False):
+        self.sizes = [int(s) for s in sizes]
+        arr = (C.c_int * len(self.sizes))(*self.sizes)
+        h = C.c_void_p()
+        check(lib.pob_mlp_create(len(self.sizes) - 1, arr, int(activation), int(bool(activate_final)), C.byref(h)))
+        self._h = h
+        n = C.c_longlong()
+        check(lib.pob_mlp_param_count(h, C.byref(n)))
+        self.param_count = int(n.value)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            lib.pob_mlp_destroy(h)
+
+
+class Params(dict):
+    """``{"hidden_i": {"kernel": (in, out), "bias": (out,)}}`` whose tensors are views into the
+    flat ``theta`` (an in-place update of either is seen by the other, and by a captured graph)."""
+
+    def __init__(self, theta: torch.Tensor, sizes: Sequence[int]):
+        super().__init__()
+        self.theta, self.sizes = theta, list(sizes)
+        off = 0
+        for i, (n_in, n_out) in enumerate(zip(sizes[:-1], sizes[1:])):
+            kernel = theta[off:off + n_in * n_out].view(n_in, n_out)
+            off += n_in * n_out
+            self[f"hidden_{i}"] = {"kernel": kernel, "bias": theta[off:off + n_out]}
+            off += n_out
+        if off != theta.numel():
+            raise ValueError(f"theta has {theta.numel()} elements, the network {off}")
+
+    def to(self, device) -> "Params":
+        return Params(self.theta.detach().to(device).contiguous(), self.sizes)
+
+
+# ---- jax.random threefry2x32 on the host (the same scheme as the device's, csrc/pob_math.h),
+# so that init() gives the same parameters from the same key with or without a GPU
+_M32 = 0xFFFFFFFF
+
+
+def _threefry(k0: int, k1: int, x0: torch.Tensor, x1: torch.Tensor):
+    ks = (k0, k1, k0 ^ k1 ^ 0x1BD11BDA)
+    rot = ((13, 15, 26, 6), (17, 29, 16, 24))
+    a, b = (x0 + ks[0]) & _M32, (x1 + ks[1]) & _M32
+    for i in range(5):
+        for r in rot[i % 2]:
+            a = (a + b) & _M32
+            b = ((b << r) | (b >> (32 - r))) & _M32
+            b = b ^ a
+        a = (a + ks[(i + 1) % 3]) & _M32
+        b = (b + ks[(i + 2) % 3] + i + 1) & _M32
+    return a, b
+
+
+def _host_bits(key, n: int) -> torch.Tensor:
+    """threefry_2x32(key, iota(n)) as int64 values below 2^32 (odd n padded with a zero count)."""
+    k0, k1 = int(key[0]), int(key[1])
+    h = (n + 1) // 2
+    x = torch.arange(2 * h, dtype=torch.int64)
+    x[n:] = 0
+    a, b = _threefry(k0, k1, x[:h], x[h:])
+    return torch.cat([a, b])[:n]
+
+
+def _host_split(key, num: int = 2) -> torch.Tensor:
+    return _host_bits(key, 2 * num).reshape(num, 2)
+
+
+def _host_uniform(key, n: int, lo: float, hi: float) -> torch.Tensor:
+    bits = _host_bits(key, n)
+    f = (((bits >> 9) | 0x3F800000).to(torch.int32).view(torch.float32)) - 1.0
+    lo_t, hi_t = torch.tensor(lo, dtype=torch.float32), torch.tensor(hi, dtype=torch.float32)
+    v = f * (hi_t - lo_t) + lo_t
+    return torch.maximum(v, lo_t)
+
+
+def _key_words(key) -> torch.Tensor:
+    key = torch.as_tensor(key)
+    if key.dtype != torch.uint32 or key.numel() != 2:
+        raise TypeError("key must be a torch.uint32 tensor of 2 words (jumpy.random_prngkey)")
+    return key.reshape(2)
+
+
+@dataclasses.dataclass
+class FeedForwardModel:
+    init: Any
+    apply: Any
+    layer_sizes: Optional[Tuple[int, ...]] = None  # (obs_size, *layer_sizes)
+    activation: Optional[int] = None               # 0 relu, 1 swish, 2 tanh
+    mlp: Optional[MLPHandle] = None
+
+
+def _forward_torch(sizes, act: int, theta_or_params, x: torch.Tensor) -> torch.Tensor:
+    theta = getattr(theta_or_params, "theta", None)
+    h, off = x, 0
+    n = len(sizes) - 1
+    for i, (n_in, n_out) in enumerate(zip(sizes[:-1], sizes[1:])):
+        if theta is not None:  # slice at call time: a view made before requires_grad_() is not tracked
+            W = theta[off:off + n_in * n_out].view(n_in, n_out)
+            off += n_in * n_out
+            b = theta[off:off + n_out]
+            off += n_out
+        else:
+            W, b = theta_or_params[f"hidden_{i}"]["kernel"], theta_or_params[f"hidden_{i}"]["bias"]
+        h = torch.addmm(b, h.reshape(-1, n_in), W).reshape(*h.shape[:-1], n_out)
+        if i != n - 1:
+            h = _TORCH_ACT[act](h)
+    return h
+
+
+def make_model(layer_sizes: Sequence[int], obs_size: int, activation: Any = "swish",
+               spectral_norm: bool = False) -> FeedForwardModel:
+    """An MLP ``obs_size -> layer_sizes[0] -> .. -> layer_sizes[-1]`` with ``activation`` after
+    every layer but the last.  ``model.init(key)`` returns ``Params`` (on the key's device):
+    kernels lecun-uniform U(-sqrt(3 / in), sqrt(3 / in)) drawn through the jumpy uniform, one
+    ``key, sub = split(key)`` per layer; biases zero.  ``model.apply(params, x)``: x (..., obs_size)
+    -> (..., layer_sizes[-1])."""
+    if spectral_norm:
+        raise NotImplementedError("spectral_norm: brax's SNDense is not part of this engine (DESIGN.md "
+                                  "\"Policy networks\")")
+    sizes = (int(obs_size),) + tuple(int(s) for s in layer_sizes)
+    act = _activation_id(activation)
+    mlp = MLPHandle(sizes, act, False)  # ValueError for widths outside 1 .. 256 or more than 8 layers
+
+    def init(key) -> Params:
+        key = _key_words(key)
+        dev = key.device
+        parts = []
+        for n_in, n_out in zip(sizes[:-1], sizes[1:]):
+            lim = math.sqrt(3.0 / n_in)
+            if dev.type == "cuda":
+                from .. import jumpy
+                key, sub = jumpy.random_split(key)
+                w = jumpy.random_uniform(sub, (n_in * n_out,), -lim, lim)
+            else:
+                key, sub = _host_split(key)
+                w = _host_uniform(sub, n_in * n_out, -lim, lim)
+            parts += [w, torch.zeros(n_out, dtype=torch.float32, device=dev)]
+        return Params(torch.cat(parts).contiguous(), sizes)
+
+    def apply(params, x: torch.Tensor) -> torch.Tensor:
+        theta = getattr(params, "theta", None)
+        need_grad = torch.is_grad_enabled() and (x.requires_grad or (
+            theta.requires_grad if theta is not None else any(t.requires_grad for p in params.values() for t in p.values())))
+        fused = (theta is not None and x.is_cuda and x.dtype == torch.float32 and theta.is_cuda
+                 and theta.dtype == torch.float32 and theta.is_contiguous() and not need_grad)
+        if not fused:
+            return _forward_torch(sizes, act, params, x)
+        if theta.numel() != mlp.param_count:
+            raise ValueError(f"theta has {theta.numel()} elements, the network {mlp.param_count}")
+        if x.shape[-1] != sizes[0]:
+            raise ValueError(f"x must be (..., {sizes[0]})")
+        x2 = x.detach().reshape(-1, sizes[0]).contiguous()
+        y = torch.empty((x2.shape[0], sizes[-1]), dtype=torch.float32, device=x.device)
+        if x2.shape[0]:
+            check(lib.pob_mlp_forward(mlp.handle, x2.shape[0], ptr(x2), ptr(theta.detach()), ptr(y),
+                                      _lib.stream_handle(x.device)))
+        return y.reshape(*x.shape[:-1], sizes[-1])
+
+    return FeedForwardModel(init=init, apply=apply, layer_sizes=sizes, activation=act, mlp=mlp)
+
+
+def make_models(policy_params_size: int, obs_size: int) -> Tuple[FeedForwardModel, FeedForwardModel]:
+    """The reference's PPO pair: policy [32] * 4 + [policy_params_size], value [256] * 5 + [1]."""
+    return (make_model([32, 32, 32, 32, policy_params_size], obs_size),
+            make_model([256, 256, 256, 256, 256, 1], obs_size))
+
+
+class NormalTanhPolicy:
+    """``policy(obs) -> action`` (B, A) on the device: the model's forward and brax's tanh-normal
+    head (loc, s = split(logits); scale = softplus(s) + 0.001; action = tanh(loc + scale eps)) in
+    ONE ``pob_policy_act`` launch, plus the one-thread key advance.  No allocation, no host sync
+    after the first call at a batch size: capture-safe.  ``.logp`` (B,) and ``.raw`` (B, A) hold
+    the last call's log-probability and pre-tanh action; ``deterministic = True`` gives
+    ``tanh(loc)`` and leaves the key and ``.logp`` alone.  The noise of env ``b`` is row
+    ``first + b`` of a draw for ``total`` envs, so a shard's actions equal the slice of the
+    whole batch's."""
+
+    def __init__(self, model: FeedForwardModel, params: Params, key, total: Optional[int] = None, first: int = 0,
+                 deterministic: bool = False):
+        if model.mlp is None or model.layer_sizes is None:
+            raise ValueError("model must come from make_model")
+        if model.layer_sizes[-1] % 2:
+            raise ValueError("the policy network's last width must be even (loc and scale halves)")
+        theta = params.theta
+        if not (theta.is_cuda and theta.dtype == torch.float32 and theta.is_contiguous()):
+            raise ValueError("params.theta must be a contiguous float32 CUDA tensor (params.to('cuda'))")
+        if theta.numel() != model.mlp.param_count:
+            raise ValueError(f"theta has {theta.numel()} elements, the network {model.mlp.param_count}")
+        self.model, self.params, self.theta = model, params, theta
+        self.obs_size, self.action_size = model.layer_sizes[0], model.layer_sizes[-1] // 2
+        self.key = _key_words(key).to(theta.device).clone()
+        self.total, self.first = (None if total is None else int(total)), int(first)
+        self.deterministic = bool(deterministic)
+        self.action = self.logp = self.raw = None
+
+    def _buffers(self, B: int):
+        if self.action is None or self.action.shape[0] != B:
+            dev = self.theta.device
+            self.action = torch.zeros((B, self.action_size), dtype=torch.float32, device=dev)
+            self.raw = torch.zeros((B, self.action_size), dtype=torch.float32, device=dev)
+            self.logp = torch.zeros((B,), dtype=torch.float32, device=dev)
+
+    def act_into(self, obs: torch.Tensor, action: torch.Tensor, logp=None, raw=None, logits=None, obs_copy=None):
+        """One launch on caller buffers (contiguous float32 device tensors; None = skip)."""
+        if not (obs.is_cuda and obs.dtype == torch.float32 and obs.dim() == 2 and obs.shape[1] == self.obs_size
+                and obs.is_contiguous()):
+            raise ValueError(f"obs must be a contiguous float32 CUDA tensor (B, {self.obs_size})")
+        B, A = int(obs.shape[0]), self.action_size
+        for t, shape in ((action, (B, A)), (logp, (B,)), (raw, (B, A)), (logits, (B, 2 * A)), (obs_copy, (B, self.obs_size))):
+            if t is not None and not (tuple(t.shape) == shape and t.dtype == torch.float32 and t.is_contiguous()
+                                      and t.device == obs.device):
+                raise ValueError(f"output buffer must be a contiguous float32 tensor {shape} on {obs.device}")
+        total = B if self.total is None else self.total
+        check(lib.pob_policy_act(self.model.mlp.handle, B, total, self.first, ptr(obs), ptr(self.theta), ptr(self.key),
+                                 int(self.deterministic), ptr(action), ptr(logp), ptr(raw), ptr(logits), ptr(obs_copy),
+                                 _lib.stream_handle(obs.device)))
+        return action
+
+    def __call__(self, obs: torch.Tensor) -> torch.Tensor:
+        self._buffers(int(obs.shape[0]))
+        return self.act_into(obs, self.action, self.logp, self.raw)

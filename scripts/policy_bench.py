@@ -1,0 +1,110 @@
+"""policy_bench.py -- what the policy in the loop costs next to the fused env step.
+
+AntHeavenHell, B = 65 536, T = 20 env-steps per replay, one process, three captured unrolls
+replayed in turn (A, B, C, A, B, C, ..), the median replay time of each:
+
+  A  rollout.PolicyRollout with the reference's policy network ([32] * 4 + [2 A], swish,
+     tanh-normal head) written in torch ops (addmm, silu, softplus, randn, tanh)
+  B  rollout.ActorRollout: the same network as ONE pob_policy_act launch per step (which also
+     gives logp, raw and the trajectory's observation rows)
+  C  rollout.GraphRollout on pre-drawn actions: the env step alone
+
+Prints one JSON line: ms/step of each and the policy's share A - C and B - C.
+
+    python scripts/policy_bench.py [--batch 65536] [--steps 20] [--rounds 15] [--out FILE]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "po-brax_amd"))
+
+
+class TorchNormalTanhPolicy:
+    """The same actor in torch ops, on the same flat parameters (action only)."""
+
+    def __init__(self, params, action_size):
+        self.layers = [(params[f"hidden_{i}"]["kernel"], params[f"hidden_{i}"]["bias"]) for i in range(len(params))]
+        self.A = action_size
+
+    def __call__(self, obs):
+        h = obs
+        for i, (W, b) in enumerate(self.layers):
+            h = torch.addmm(b, h, W)
+            if i != len(self.layers) - 1:
+                h = torch.nn.functional.silu(h)
+        loc, s = h[:, :self.A], h[:, self.A:]
+        scale = torch.nn.functional.softplus(s) + 0.001
+        return torch.tanh(loc + scale * torch.randn_like(loc))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--env", default="ant_heavenhell")
+    ap.add_argument("--batch", type=int, default=65536)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=15)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+
+    from po_brax_amd import envs, jumpy
+    from po_brax_amd.rollout import ActorRollout, GraphRollout, PolicyRollout
+    from po_brax_amd.training import networks
+
+    B, T = args.batch, args.steps
+    keys = jumpy.random_split(jumpy.random_prngkey(0), B + 1)[1:]
+    es = [envs.create(args.env, batch_size=B) for _ in range(3)]
+    ss = [e.reset(keys) for e in es]
+    A, D = es[0].action_size, es[0].observation_size
+    model = networks.make_models(2 * A, D)[0]
+    params = model.init(jumpy.random_prngkey(1))
+    with torch.no_grad():
+        roll_a = PolicyRollout(es[0], ss[0], TorchNormalTanhPolicy(params, A), T)
+    roll_b = ActorRollout(es[1], ss[1], networks.NormalTanhPolicy(model, params, jumpy.random_prngkey(2)), T)
+    acts = torch.rand((T, B, A), device="cuda") * 2 - 1
+    roll_c = GraphRollout(es[2], ss[2], acts, warmup=True)
+    rolls = {"A": roll_a, "B": roll_b, "C": roll_c}
+
+    def timed(roll):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        roll.replay()
+        t1.record()
+        t1.synchronize()
+        return t0.elapsed_time(t1) / T
+
+    for _ in range(args.warmup):
+        for r in rolls.values():
+            timed(r)
+    ms = {k: [] for k in rolls}
+    for _ in range(args.rounds):
+        for k, r in rolls.items():
+            ms[k].append(timed(r))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    res = {
+        "bench": "policy_bench", "env": args.env, "batch": B, "steps": T, "rounds": args.rounds,
+        "device": torch.cuda.get_device_name(0),
+        "A_policy_rollout_torch_ms_per_step": round(med["A"], 5),
+        "B_actor_rollout_ms_per_step": round(med["B"], 5),
+        "C_graph_rollout_ms_per_step": round(med["C"], 5),
+        "policy_share_torch_ms": round(med["A"] - med["C"], 5),
+        "policy_share_native_ms": round(med["B"] - med["C"], 5),
+        "min_ms_per_step": {k: round(min(v), 5) for k, v in ms.items()},
+        "max_ms_per_step": {k: round(max(v), 5) for k, v in ms.items()},
+    }
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
