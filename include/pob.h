@@ -233,6 +233,34 @@ int pob_policy_act(const pob_mlp *mlp, int B, int total, int first, const float 
                    uint32_t *key_io, int deterministic, float *action, float *logp, float *raw, float *logits,
                    float *obs_copy, void *stream);
 
+/* ---- recurrent actor (additive to ABI v8): obs (D) -> pre-MLP (0 .. 3 dense layers, the
+ * activation after every one) -> GRU cell (hidden width H; input x of width I = the pre-MLP's
+ * output, or D without one) -> post-MLP (1 .. 4 dense layers, the activation after all but the
+ * last), every layer and the cell in one launch; results equal gru_forward_ref of
+ * csrc/pob_mlp.h bit for bit (DESIGN.md "Recurrent actor").  The cell, with c = [x ; h]:
+ *   r = sigmoid(b_rz[:H] + c W_rz[:, :H]),  z = sigmoid(b_rz[H:] + c W_rz[:, H:]),
+ *   n = tanh(r (b_hn + h W_hn) + (b_xn + x W_xn)),  h' = z (h - n) + n.
+ * `theta`: the pre-MLP's W, b pairs, W_rz (I + H, 2 H), b_rz (2 H), W_xn (I, H), b_xn (H),
+ * W_hn (H, H), b_hn (H), the post-MLP's pairs; every matrix row-major (in, out).
+ * Limits: every dense width and D in 1 .. 256, 1 <= H <= 128, I + H <= 256.
+ * h_io (B, H) is read, then overwritten in place with h'.  reset (B, may be NULL): where
+ * reset[b] != 0 (a NaN too) env b starts from h = +0.  h_in_copy (B, H, may be NULL) receives
+ * the h the step started from, after the reset.  Rows >= B are never written.
+ * pob_gru_create / pob_gru_destroy never call the HIP runtime. */
+typedef struct pob_gru pob_gru;
+int pob_gru_create(int n_pre, const int *pre_sizes /* n_pre + 1, [0] = obs width */, int hidden, int n_post,
+                   const int *post_sizes /* n_post widths after the cell */, int activation, pob_gru **out);
+void pob_gru_destroy(pob_gru *g);
+int pob_gru_param_count(const pob_gru *g, long long *n);
+/* y (B, post_sizes[n_post - 1]) */
+int pob_gru_forward(const pob_gru *g, int B, const float *x, const float *theta, const float *reset, float *h_io,
+                    float *y, float *h_in_copy, void *stream);
+/* pob_policy_act with the recurrent network: noise, shard indexing, deterministic, the key
+ * advance and the optional outputs are pob_policy_act's.  The last post width must be even. */
+int pob_gru_policy_act(const pob_gru *g, int B, int total, int first, const float *obs, const float *theta,
+                       uint32_t *key_io, int deterministic, const float *reset, float *h_io, float *action,
+                       float *logp, float *raw, float *logits, float *obs_copy, float *h_in_copy, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 // pob_mlp.h -- the scalar math and the plain-C restatement of the policy-network kernels
-// (pob_mlp.hip: k_mlp_forward, k_policy_act).  Compiled for the device by hipcc and, with
-// POB_MLP_HOST, for the host by g++ (tests/host/mlp_host.cpp); both with -ffp-contract=off.
+// (pob_mlp.hip: k_mlp_forward, k_policy_act, and the recurrent k_gru_forward, k_gru_policy_act).
+// Compiled for the device by hipcc and, with POB_MLP_HOST, for the host by g++
+// (tests/host/mlp_host.cpp, gru_host.cpp); both with -ffp-contract=off.
 //
 // Every function is a fixed sequence of float32 +, *, fmaf, integer bit operations, and the
 // correctly rounded reciprocal and square root (pob_rcp / pob_sqrt of pob_math.h on the device,
@@ -34,6 +35,9 @@ POB_MLP_D float mlp_u2f(uint32_t u) { return __uint_as_float(u); }
 
 #define POB_MLP_MAX_LAYERS 8
 #define POB_MLP_MAX_WIDTH 256
+#define POB_GRU_MAX_HIDDEN 128  // the recurrent actor: hidden width, pre- and post-MLP depths
+#define POB_GRU_MAX_PRE 3
+#define POB_GRU_MAX_POST 4
 enum { POB_ACT_RELU = 0, POB_ACT_SWISH = 1, POB_ACT_TANH = 2 };
 
 // input feature of k-step s, lane half h (the summation order: s ascending, h = 0 then 1)
@@ -233,5 +237,108 @@ static inline void policy_head_ref(const int B, const int A, const float *logits
     }
     if (!deterministic) logp[b] = sum;
   }
+}
+
+// ---------------------------------------------------------------------------- recurrent actor
+// obs -> pre-MLP (n_pre layers, pre_sizes[0] = obs width, activation after every one) -> GRU
+// cell (hidden width H, input x of width I = pre_sizes[n_pre]) -> post-MLP (n_post layers of
+// widths post_sizes[0 .. n_post), activation after all but the last).  theta: the pre-MLP's W, b
+// pairs, W_rz (I + H, 2 H), b_rz (2 H), W_xn (I, H), b_xn (H), W_hn (H, H), b_hn (H), the
+// post-MLP's pairs; every matrix row-major (in, out).  The cell, with c = [x ; h]:
+//   r[j]  = sigmoid(b_rz[j]     + sum_k c[k] W_rz[k][j])
+//   z[j]  = sigmoid(b_rz[H + j] + sum_k c[k] W_rz[k][H + j])
+//   cx[j] = b_xn[j] + sum_k x[k] W_xn[k][j],   ch[j] = b_hn[j] + sum_k h[k] W_hn[k][j]
+//   n[j]  = tanh(fmaf(r[j], ch[j], cx[j])),    h'[j] = fmaf(z[j], h[j] - n[j], n[j])
+// every sum the chain of mlp_chain_ref (DESIGN.md "Recurrent actor").
+static inline long long gru_param_count(const int n_pre, const int *pre_sizes, const int H, const int n_post,
+                                        const int *post_sizes) {
+  long long n = 0;
+  for (int l = 0; l < n_pre; ++l) n += ((long long)pre_sizes[l] + 1) * pre_sizes[l + 1];
+  const long long I = pre_sizes[n_pre];
+  n += 3 * H * I + 3LL * H * H + 4 * H;
+  int in = H;
+  for (int l = 0; l < n_post; ++l) { n += ((long long)in + 1) * post_sizes[l]; in = post_sizes[l]; }
+  return n;
+}
+// the chain of mlp_forward_ref: bias, then one fmaf per feature of `a` (width in) in natural
+// order, column j of W (row stride ldw), an odd length padded with fmaf(0, 0, acc)
+static inline float mlp_chain_ref(const float bias, const float *W, const int ldw, const int j, const float *a, const int in) {
+  float acc = bias;
+  for (int s = 0; s < mlp_ksteps(in); ++s)
+    for (int h = 0; h < 2; ++h) {
+      const int k = mlp_kfeat(s, h);
+      acc = k < in ? MLP_FMA(W[(long long)k * ldw + j], a[k], acc) : MLP_FMA(0.0f, 0.0f, acc);
+    }
+  return acc;
+}
+// One env's cell: c = [x ; h] (I + H contiguous floats), g = the GRU block of theta.  Writes
+// r, z, cx, ch, hn (H each).
+static inline void gru_cell_ref(const int I, const int H, const float *c, const float *g, float *r, float *z, float *cx,
+                                float *ch, float *hn) {
+  const float *W_rz = g, *b_rz = W_rz + (long long)(I + H) * 2 * H;
+  const float *W_xn = b_rz + 2 * H, *b_xn = W_xn + (long long)I * H;
+  const float *W_hn = b_xn + H, *b_hn = W_hn + (long long)H * H;
+  for (int j = 0; j < H; ++j) {
+    r[j] = pob_sigmoidf(mlp_chain_ref(b_rz[j], W_rz, 2 * H, j, c, I + H));
+    z[j] = pob_sigmoidf(mlp_chain_ref(b_rz[H + j], W_rz, 2 * H, H + j, c, I + H));
+    cx[j] = mlp_chain_ref(b_xn[j], W_xn, H, j, c, I);
+    ch[j] = mlp_chain_ref(b_hn[j], W_hn, H, j, c + I, H);
+    const float n = pob_tanhf(MLP_FMA(r[j], ch[j], cx[j]));
+    hn[j] = MLP_FMA(z[j], c[I + j] - n, n);
+  }
+}
+// y (B, post_sizes[n_post - 1]), h_out (B, H) = the network on x (B, pre_sizes[0]) and h_in (B, H);
+// reset (B) may be NULL: where reset[b] != 0 (a NaN too) env b starts from h = +0.  h_in_copy
+// (B, H, may be NULL) receives the h the step started from, after the reset.  h_out may be h_in.
+static inline void gru_forward_ref(const int n_pre, const int *pre_sizes, const int H, const int n_post,
+                                   const int *post_sizes, const int activation, const int B, const float *x,
+                                   const float *theta, const float *reset, const float *h_in, float *y, float *h_out,
+                                   float *h_in_copy) {
+  float a[POB_MLP_MAX_WIDTH + 1], o[POB_MLP_MAX_WIDTH + 1], c[POB_MLP_MAX_WIDTH + 1];
+  float r[POB_GRU_MAX_HIDDEN], z[POB_GRU_MAX_HIDDEN], cx[POB_GRU_MAX_HIDDEN], ch[POB_GRU_MAX_HIDDEN], hn[POB_GRU_MAX_HIDDEN];
+  const int D = pre_sizes[0], I = pre_sizes[n_pre], out_w = post_sizes[n_post - 1];
+  for (int b = 0; b < B; ++b) {
+    for (int k = 0; k < D; ++k) a[k] = x[(long long)b * D + k];
+    const float *W = theta;
+    for (int l = 0; l < n_pre; ++l) {
+      const int in = pre_sizes[l], out = pre_sizes[l + 1];
+      const float *bias = W + (long long)in * out;
+      for (int j = 0; j < out; ++j) o[j] = mlp_activate(activation, mlp_chain_ref(bias[j], W, out, j, a, in));
+      for (int j = 0; j < out; ++j) a[j] = o[j];
+      W = bias + out;
+    }
+    for (int k = 0; k < I; ++k) c[k] = a[k];
+    const bool zero = reset && reset[b] != 0.0f;
+    for (int k = 0; k < H; ++k) {
+      c[I + k] = zero ? 0.0f : h_in[(long long)b * H + k];
+      if (h_in_copy) h_in_copy[(long long)b * H + k] = c[I + k];
+    }
+    gru_cell_ref(I, H, c, W, r, z, cx, ch, hn);
+    W += 3LL * H * I + 3LL * H * H + 4 * H;
+    for (int k = 0; k < H; ++k) { h_out[(long long)b * H + k] = hn[k]; a[k] = hn[k]; }
+    int in = H;
+    for (int l = 0; l < n_post; ++l) {
+      const int out = post_sizes[l];
+      const float *bias = W + (long long)in * out;
+      for (int j = 0; j < out; ++j) {
+        const float acc = mlp_chain_ref(bias[j], W, out, j, a, in);
+        o[j] = l != n_post - 1 ? mlp_activate(activation, acc) : acc;
+      }
+      for (int j = 0; j < out; ++j) a[j] = o[j];
+      W = bias + out;
+      in = out;
+    }
+    for (int j = 0; j < out_w; ++j) y[(long long)b * out_w + j] = a[j];
+  }
+}
+// The recurrent actor: gru_forward_ref's y is the logits (B, 2 A), then policy_head_ref on the
+// uniform draws u (B, A).
+static inline void gru_policy_ref(const int n_pre, const int *pre_sizes, const int H, const int n_post,
+                                  const int *post_sizes, const int activation, const int B, const float *obs,
+                                  const float *theta, const float *reset, const float *h_in, const float *u,
+                                  const int deterministic, float *logits, float *h_out, float *h_in_copy, float *action,
+                                  float *logp, float *raw) {
+  gru_forward_ref(n_pre, pre_sizes, H, n_post, post_sizes, activation, B, obs, theta, reset, h_in, logits, h_out, h_in_copy);
+  policy_head_ref(B, post_sizes[n_post - 1] >> 1, logits, u, deterministic, action, logp, raw);
 }
 #endif

@@ -3,6 +3,7 @@
 //
 //   k_mlp_forward   y = MLP(x): every layer in one launch
 //   k_policy_act    the same forward, then the tanh-normal head (brax NormalTanhDistribution [ext])
+//   k_gru_forward, k_gru_policy_act   the recurrent actor (pre-MLP, GRU cell, post-MLP; below)
 //
 // One 64-lane block (one wave) owns a tile of 32 batch rows.  It computes Y^T = W^T X^T with
 // v_mfma_f32_32x32x2_f32: the env is the C column (lane & 31), the A operand of k-step s is row
@@ -50,33 +51,44 @@ struct MlpDesc {
 // register r of lane half h holds output feature (r & 3) + 8 (r >> 2) + 4 h of the 32-feature tile
 POB_MLP_D int mlp_acc_row(const int r, const int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
+// One output tile's chain: acc += sum over the `in` features of src of W[k][col] src[k][env], in
+// the order of mlp_kfeat (W's rows are ldw floats apart; cok: this lane's column exists).
+POB_MLP_D void mlp_chain(mlp_f32x16 &acc, const float *src, const float *W, const int ldw, const int col, const bool cok,
+                         const int in, const int lane) {
+  const int j = lane & 31, h = lane >> 5;
+  const int ks = mlp_ksteps(in);
+  for (int s0 = 0; s0 < ks; s0 += MLP_KUNROLL) {
+    float a[MLP_KUNROLL], b[MLP_KUNROLL];
+#pragma unroll
+    for (int u = 0; u < MLP_KUNROLL; ++u) {
+      const int k = mlp_kfeat(s0 + u, h);
+      const bool kok = k < in;
+      a[u] = (kok && cok) ? W[(size_t)k * ldw + col] : 0.0f;
+      b[u] = kok ? src[k * MLP_PITCH + j] : 0.0f;
+    }
+#pragma unroll
+    for (int u = 0; u < MLP_KUNROLL; ++u)
+      if (s0 + u < ks) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b[u], acc, 0, 0, 0);
+  }
+}
+
+// the accumulator of output tile ot started from the bias (0 past the layer's width)
+POB_MLP_D void mlp_acc_bias(mlp_f32x16 &acc, const float *bias, const int ot, const int out, const int h) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int i = ot + mlp_acc_row(r, h);
+    acc[r] = i < out ? bias[i] : 0.0f;
+  }
+}
+
 // one layer: src image (in features) -> dst image (out features)
 POB_MLP_D void mlp_layer(const float *src, float *dst, const float *W, const float *bias, const int in, const int out,
                          const bool activate, const int act, const int lane) {
   const int j = lane & 31, h = lane >> 5;
-  const int ks = mlp_ksteps(in);
   for (int ot = 0; ot < out; ot += 32) {
     mlp_f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int i = ot + mlp_acc_row(r, h);
-      acc[r] = i < out ? bias[i] : 0.0f;
-    }
-    const int col = ot + j;  // this lane's row of W^T
-    const bool cok = col < out;
-    for (int s0 = 0; s0 < ks; s0 += MLP_KUNROLL) {
-      float a[MLP_KUNROLL], b[MLP_KUNROLL];
-#pragma unroll
-      for (int u = 0; u < MLP_KUNROLL; ++u) {
-        const int k = mlp_kfeat(s0 + u, h);
-        const bool kok = k < in;
-        a[u] = (kok && cok) ? W[(size_t)k * out + col] : 0.0f;
-        b[u] = kok ? src[k * MLP_PITCH + j] : 0.0f;
-      }
-#pragma unroll
-      for (int u = 0; u < MLP_KUNROLL; ++u)
-        if (s0 + u < ks) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b[u], acc, 0, 0, 0);
-    }
+    mlp_acc_bias(acc, bias, ot, out, h);
+    mlp_chain(acc, src, W, out, ot + j, ot + j < out, in, lane);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int i = ot + mlp_acc_row(r, h);
@@ -95,11 +107,12 @@ POB_MLP_D void mlp_tile_store(float *dst, const float *img, const int f0, const 
   }
 }
 
-// The forward of one tile.  Returns the image holding the last layer's output.
-POB_MLP_D float *mlp_tile_forward(const MlpDesc &d, float *imgA, float *imgB, const int B, const int b0, const float *x,
-                                  const float *theta, float *obs_copy, const int lane) {
-  const int D = d.sizes[0];
-  const int valid = B - b0 < MLP_ROWS ? B - b0 : MLP_ROWS;
+// features [0, D) of an image <- rows [b0, b0 + 32) of a row-major (B, D) array x: coalesced
+// loads, MLP_STAGE in flight per lane, tail rows repeating the last valid one.  copy (may be
+// NULL) receives the valid rows as staged.  reset (may be NULL): a row whose reset[b] != 0 is
+// staged as +0 in every feature.
+POB_MLP_D void mlp_tile_load(float *img, const float *x, const int D, const int b0, const int valid, float *copy,
+                             const float *reset, const int lane) {
   // element e = row D + col of the tile's 32 contiguous rows; a lane's elements are 64 apart
   const int dq = 64 / D, dr = 64 - dq * D;
   int row = lane / D, col = lane - row * D;
@@ -111,6 +124,7 @@ POB_MLP_D float *mlp_tile_forward(const MlpDesc &d, float *imgA, float *imgB, co
       const bool in_tile = e0 + 64 * u < MLP_ROWS * D;
       const int rr = row < valid ? row : valid - 1;  // tail rows repeat the last one
       v[u] = in_tile ? x[(size_t)(b0 + rr) * D + col] : 0.0f;
+      if (reset) v[u] = (in_tile && reset[b0 + rr] != 0.0f) ? 0.0f : v[u];
       at[u] = in_tile ? (col * MLP_PITCH + row) | (row < valid ? 1 << 30 : 0) : -1;
       row += dq; col += dr;
       if (col >= D) { col -= D; ++row; }
@@ -118,11 +132,18 @@ POB_MLP_D float *mlp_tile_forward(const MlpDesc &d, float *imgA, float *imgB, co
 #pragma unroll
     for (int u = 0; u < MLP_STAGE; ++u) {
       if (at[u] >= 0) {
-        imgA[at[u] & 0xFFFFF] = v[u];
-        if (obs_copy && (at[u] >> 30)) obs_copy[(size_t)b0 * D + e0 + 64 * u] = v[u];
+        img[at[u] & 0xFFFFF] = v[u];
+        if (copy && (at[u] >> 30)) copy[(size_t)b0 * D + e0 + 64 * u] = v[u];
       }
     }
   }
+}
+
+// The forward of one tile.  Returns the image holding the last layer's output.
+POB_MLP_D float *mlp_tile_forward(const MlpDesc &d, float *imgA, float *imgB, const int B, const int b0, const float *x,
+                                  const float *theta, float *obs_copy, const int lane) {
+  const int valid = B - b0 < MLP_ROWS ? B - b0 : MLP_ROWS;
+  mlp_tile_load(imgA, x, d.sizes[0], b0, valid, obs_copy, nullptr, lane);
   __syncthreads();
   float *src = imgA, *dst = imgB;
   const float *W = theta;
@@ -148,21 +169,14 @@ __global__ __launch_bounds__(64) void k_mlp_forward(const MlpDesc d, const int s
   mlp_tile_store(y, out, 0, d.sizes[d.n_layers], b0, valid, lane);
 }
 
-// Env b of this launch is env first + b of a batch of `total`: its draw for action component a
-// is element (first + b) A + a of uniform(split(key)[1], (total, A), -1, 1).  The key is only
-// read here (k_mlp_advance_key, launched after, advances it).
-template <int H>
-__global__ __launch_bounds__(64) void k_policy_act(const MlpDesc d, const int split, const int B, const int total,
-                                                   const int first, const float *obs, const float *theta,
-                                                   const uint32_t *key, const int deterministic, float *action,
-                                                   float *logp, float *raw, float *logits, float *obs_copy) {
-  __shared__ float img[H * MLP_PITCH];
-  float *imgA = img, *imgB = img + split * MLP_PITCH;
-  const int lane = threadIdx.x, b0 = blockIdx.x * MLP_ROWS;
-  float *L = mlp_tile_forward(d, imgA, imgB, B, b0, obs, theta, obs_copy, lane);
-  float *T = L == imgA ? imgB : imgA;  // the per-component log-probability terms
-  const int valid = B - b0 < MLP_ROWS ? B - b0 : MLP_ROWS;
-  const int A = d.sizes[d.n_layers] >> 1;
+// The tanh-normal head of one tile: L holds the logits (2 A features), T (A features, another
+// image) takes the per-component log-probability terms.  Env b of this launch is env first + b
+// of a batch of `total`: its draw for action component a is element (first + b) A + a of
+// uniform(split(key)[1], (total, A), -1, 1).  The key is only read here (k_mlp_advance_key,
+// launched after, advances it).
+POB_MLP_D void policy_tile_head(float *L, float *T, const int A, const int b0, const int valid, const int total,
+                                const int first, const uint32_t *key, const int deterministic, float *action, float *logp,
+                                float *raw, float *logits, const int lane) {
   if (logits) {
     mlp_tile_store(logits, L, 0, 2 * A, b0, valid, lane);
     __syncthreads();
@@ -197,10 +211,144 @@ __global__ __launch_bounds__(64) void k_policy_act(const MlpDesc d, const int sp
   }
 }
 
+template <int H>
+__global__ __launch_bounds__(64) void k_policy_act(const MlpDesc d, const int split, const int B, const int total,
+                                                   const int first, const float *obs, const float *theta,
+                                                   const uint32_t *key, const int deterministic, float *action,
+                                                   float *logp, float *raw, float *logits, float *obs_copy) {
+  __shared__ float img[H * MLP_PITCH];
+  float *imgA = img, *imgB = img + split * MLP_PITCH;
+  const int lane = threadIdx.x, b0 = blockIdx.x * MLP_ROWS;
+  float *L = mlp_tile_forward(d, imgA, imgB, B, b0, obs, theta, obs_copy, lane);
+  float *T = L == imgA ? imgB : imgA;  // the per-component log-probability terms
+  const int valid = B - b0 < MLP_ROWS ? B - b0 : MLP_ROWS;
+  const int A = d.sizes[d.n_layers] >> 1;
+  policy_tile_head(L, T, A, b0, valid, total, first, key, deterministic, action, logp, raw, logits, lane);
+}
+
 __global__ void k_mlp_advance_key(uint32_t *key) {
   uint32_t o0, o1;
   tf_split(key[0], key[1], 2u, 0u, o0, o1);
   key[0] = o0; key[1] = o1;
+}
+
+// ============================================================================ recurrent actor
+// obs -> pre-MLP -> GRU cell -> post-MLP (pob_mlp.h gru_forward_ref is the specification).  The
+// pool holds four regions, in this order: C = [x ; h] (I + H features: the cell's input image,
+// h staged directly behind x), N (H features: h'), and the ping-pong images P0, P1 of the dense
+// layers' other activations (heights p_rows[0], p_rows[1], worked out by gru_plan on the host
+// with the walk gru_tile_forward makes).
+struct GruDesc {
+  int n_pre, n_post, hid, act;
+  int pre[POB_GRU_MAX_PRE + 1];  // pre[0] = obs width, pre[n_pre] = I
+  int post[POB_GRU_MAX_POST];
+  int p_rows[2];
+};
+
+// The cell on one tile: C (I + H features) -> N (H features).  g: the GRU block of theta.  Per
+// 32-feature output tile four accumulators (r, z, cx, ch) take their chains, then n and h' are
+// finished in registers, the old h read from C.
+POB_MLP_D void gru_cell(const float *C, float *N, const float *g, const int I, const int H, const int lane) {
+  const int j = lane & 31, h = lane >> 5;
+  const float *W_rz = g, *b_rz = W_rz + (size_t)(I + H) * 2 * H;
+  const float *W_xn = b_rz + 2 * H, *b_xn = W_xn + (size_t)I * H;
+  const float *W_hn = b_xn + H, *b_hn = W_hn + (size_t)H * H;
+  for (int ot = 0; ot < H; ot += 32) {
+    const int col = ot + j;
+    const bool cok = col < H;
+    mlp_f32x16 ar, az, ax, ah;
+    mlp_acc_bias(ar, b_rz, ot, H, h);
+    mlp_chain(ar, C, W_rz, 2 * H, col, cok, I + H, lane);
+    mlp_acc_bias(az, b_rz + H, ot, H, h);
+    mlp_chain(az, C, W_rz, 2 * H, H + col, cok, I + H, lane);
+    mlp_acc_bias(ax, b_xn, ot, H, h);
+    mlp_chain(ax, C, W_xn, H, col, cok, I, lane);
+    mlp_acc_bias(ah, b_hn, ot, H, h);
+    mlp_chain(ah, C + I * MLP_PITCH, W_hn, H, col, cok, H, lane);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int i = ot + mlp_acc_row(r, h);
+      if (i < H) {
+        const float rg = pob_sigmoidf(ar[r]), zg = pob_sigmoidf(az[r]);
+        const float n = pob_tanhf(MLP_FMA(rg, ah[r], ax[r]));
+        const float hold = C[(I + i) * MLP_PITCH + j];
+        N[i * MLP_PITCH + j] = MLP_FMA(zg, hold - n, n);
+      }
+    }
+  }
+}
+
+// The forward of one tile; h' is stored to h_io on the way.  Returns the image holding the post-
+// MLP's output; `other` is the ping-pong image it is not in.
+POB_MLP_D float *gru_tile_forward(const GruDesc &d, float *pool, const int B, const int b0, const float *x,
+                                  const float *theta, const float *reset, float *h_io, float *obs_copy, float *h_in_copy,
+                                  float *&other, const int lane) {
+  const int valid = B - b0 < MLP_ROWS ? B - b0 : MLP_ROWS;
+  const int I = d.pre[d.n_pre], H = d.hid;
+  float *C = pool, *N = C + (I + H) * MLP_PITCH;
+  float *P0 = N + H * MLP_PITCH, *P1 = P0 + d.p_rows[0] * MLP_PITCH;
+  int pp = 0;
+  mlp_tile_load(d.n_pre ? P0 : C, x, d.pre[0], b0, valid, obs_copy, nullptr, lane);
+  mlp_tile_load(C + I * MLP_PITCH, h_io, H, b0, valid, h_in_copy, reset, lane);
+  __syncthreads();
+  const float *W = theta;
+  float *src = P0;
+  if (d.n_pre) pp = 1;
+  for (int l = 0; l < d.n_pre; ++l) {
+    const int in = d.pre[l], out = d.pre[l + 1];
+    const float *bias = W + (size_t)in * out;
+    float *dst = l == d.n_pre - 1 ? C : (pp ? P1 : P0);
+    mlp_layer(src, dst, W, bias, in, out, true, d.act, lane);
+    __syncthreads();
+    W = bias + out;
+    src = dst;
+    pp ^= 1;
+  }
+  gru_cell(C, N, W, I, H, lane);
+  __syncthreads();
+  W += (size_t)3 * H * I + (size_t)3 * H * H + 4 * H;
+  mlp_tile_store(h_io, N, 0, H, b0, valid, lane);
+  src = N;
+  int in = H;
+  for (int l = 0; l < d.n_post; ++l) {
+    const int out = d.post[l];
+    const float *bias = W + (size_t)in * out;
+    float *dst = pp ? P1 : P0;
+    mlp_layer(src, dst, W, bias, in, out, l != d.n_post - 1, d.act, lane);
+    __syncthreads();
+    W = bias + out;
+    src = dst;
+    in = out;
+    pp ^= 1;
+  }
+  other = pp ? P1 : P0;
+  return src;
+}
+
+template <int R>
+__global__ __launch_bounds__(64) void k_gru_forward(const GruDesc d, const int B, const float *x, const float *theta,
+                                                    const float *reset, float *h_io, float *y, float *h_in_copy) {
+  __shared__ float pool[R * MLP_PITCH];
+  const int lane = threadIdx.x, b0 = blockIdx.x * MLP_ROWS;
+  float *other;
+  const float *out = gru_tile_forward(d, pool, B, b0, x, theta, reset, h_io, nullptr, h_in_copy, other, lane);
+  const int valid = B - b0 < MLP_ROWS ? B - b0 : MLP_ROWS;
+  mlp_tile_store(y, out, 0, d.post[d.n_post - 1], b0, valid, lane);
+}
+
+template <int R>
+__global__ __launch_bounds__(64) void k_gru_policy_act(const GruDesc d, const int B, const int total, const int first,
+                                                       const float *obs, const float *theta, const uint32_t *key,
+                                                       const int deterministic, const float *reset, float *h_io,
+                                                       float *action, float *logp, float *raw, float *logits,
+                                                       float *obs_copy, float *h_in_copy) {
+  __shared__ float pool[R * MLP_PITCH];
+  const int lane = threadIdx.x, b0 = blockIdx.x * MLP_ROWS;
+  float *T;  // the per-component log-probability terms
+  float *L = gru_tile_forward(d, pool, B, b0, obs, theta, reset, h_io, obs_copy, h_in_copy, T, lane);
+  const int valid = B - b0 < MLP_ROWS ? B - b0 : MLP_ROWS;
+  const int A = d.post[d.n_post - 1] >> 1;
+  policy_tile_head(L, T, A, b0, valid, total, first, key, deterministic, action, logp, raw, logits, lane);
 }
 
 // ============================================================================ C ABI
@@ -303,6 +451,128 @@ int pob_policy_act(const pob_mlp *m, int B, int total, int first, const float *o
                obs_copy)
   if (!deterministic) hipLaunchKernelGGL(k_mlp_advance_key, dim3(1), dim3(1), 0, st, key_io);
   return mlp_hip_check(hipGetLastError(), "k_policy_act launch");
+}
+
+}  // extern "C"
+
+struct pob_gru {
+  GruDesc d;
+  long long n_params;
+  int cls_forward, cls_actor;  // pool height classes (GRU_DISPATCH)
+};
+
+// The heights of P0 and P1, by the walk of gru_tile_forward; with `head` the actor's terms (A
+// features) go to the image the logits are not in.  Returns the pool's height class (0 .. 4:
+// 96 / 192 / 288 / 512 / 896 rows; the widest legal network takes 256 + 128 + 256 + 256).
+static int gru_plan(const GruDesc &d, bool head, int *p_rows) {
+  int w[2] = {0, 0}, pp = 0;
+  if (d.n_pre) { w[0] = d.pre[0]; pp = 1; }
+  for (int l = 0; l < d.n_pre; ++l) {
+    if (l != d.n_pre - 1 && d.pre[l + 1] > w[pp]) w[pp] = d.pre[l + 1];
+    pp ^= 1;
+  }
+  for (int l = 0; l < d.n_post; ++l) {
+    if (d.post[l] > w[pp]) w[pp] = d.post[l];
+    pp ^= 1;
+  }
+  const int A = d.post[d.n_post - 1] >> 1;
+  if (head && A > w[pp]) w[pp] = A;
+  if (p_rows) { p_rows[0] = w[0]; p_rows[1] = w[1]; }
+  const int rows = d.pre[d.n_pre] + 2 * d.hid + w[0] + w[1];
+  return rows <= 96 ? 0 : (rows <= 192 ? 1 : (rows <= 288 ? 2 : (rows <= 512 ? 3 : 4)));
+}
+
+#define GRU_DISPATCH(KERNEL, cls, ...)                                                      \
+  switch (cls) {                                                                            \
+    case 0: hipLaunchKernelGGL((KERNEL<96>), grid, dim3(64), 0, st, __VA_ARGS__); break;    \
+    case 1: hipLaunchKernelGGL((KERNEL<192>), grid, dim3(64), 0, st, __VA_ARGS__); break;   \
+    case 2: hipLaunchKernelGGL((KERNEL<288>), grid, dim3(64), 0, st, __VA_ARGS__); break;   \
+    case 3: hipLaunchKernelGGL((KERNEL<512>), grid, dim3(64), 0, st, __VA_ARGS__); break;   \
+    default: hipLaunchKernelGGL((KERNEL<896>), grid, dim3(64), 0, st, __VA_ARGS__); break;  \
+  }
+
+extern "C" {
+
+int pob_gru_create(int n_pre, const int *pre_sizes, int hidden, int n_post, const int *post_sizes, int activation,
+                   pob_gru **out) {
+  if (!out) return pob_fail_msg(POB_EINVAL, "gru: out is NULL");
+  *out = nullptr;
+  if (!pre_sizes || !post_sizes) return pob_fail_msg(POB_EINVAL, "gru: sizes is NULL");
+  if (n_pre < 0 || n_pre > POB_GRU_MAX_PRE || n_post < 1 || n_post > POB_GRU_MAX_POST)
+    return pob_fail_msg(POB_EINVAL, "gru: 0 to 3 pre-MLP and 1 to 4 post-MLP layers (at most 8 layers with the cell)");
+  for (int l = 0; l <= n_pre; ++l)
+    if (pre_sizes[l] < 1 || pre_sizes[l] > POB_MLP_MAX_WIDTH)
+      return pob_fail_msg(POB_EINVAL, "gru: every width must be in 1 .. 256");
+  for (int l = 0; l < n_post; ++l)
+    if (post_sizes[l] < 1 || post_sizes[l] > POB_MLP_MAX_WIDTH)
+      return pob_fail_msg(POB_EINVAL, "gru: every width must be in 1 .. 256");
+  if (hidden < 1 || hidden > POB_GRU_MAX_HIDDEN) return pob_fail_msg(POB_EINVAL, "gru: the hidden width must be in 1 .. 128");
+  if (pre_sizes[n_pre] + hidden > POB_MLP_MAX_WIDTH)
+    return pob_fail_msg(POB_EINVAL, "gru: the cell's input and hidden widths together must be at most 256");
+  if (activation != POB_ACT_RELU && activation != POB_ACT_SWISH && activation != POB_ACT_TANH)
+    return pob_fail_msg(POB_EINVAL, "gru: unknown activation (0 relu, 1 swish, 2 tanh)");
+  pob_gru *g = new (std::nothrow) pob_gru();
+  if (!g) return pob_fail_msg(POB_ENOMEM, "gru: out of memory");
+  GruDesc &d = g->d;
+  d.n_pre = n_pre; d.n_post = n_post; d.hid = hidden; d.act = activation;
+  for (int l = 0; l <= POB_GRU_MAX_PRE; ++l) d.pre[l] = l <= n_pre ? pre_sizes[l] : 0;
+  for (int l = 0; l < POB_GRU_MAX_POST; ++l) d.post[l] = l < n_post ? post_sizes[l] : 0;
+  long long n = 0;
+  for (int l = 0; l < n_pre; ++l) n += ((long long)d.pre[l] + 1) * d.pre[l + 1];
+  const long long I = d.pre[n_pre], H = hidden;
+  n += 3 * H * I + 3 * H * H + 4 * H;
+  long long in = H;
+  for (int l = 0; l < n_post; ++l) { n += (in + 1) * d.post[l]; in = d.post[l]; }
+  g->n_params = n;
+  g->cls_forward = gru_plan(d, false, nullptr);
+  g->cls_actor = gru_plan(d, true, nullptr);
+  *out = g;
+  return POB_OK;
+}
+
+void pob_gru_destroy(pob_gru *g) { delete g; }
+
+int pob_gru_param_count(const pob_gru *g, long long *n) {
+  if (!g || !n) return pob_fail_msg(POB_EINVAL, "gru: NULL argument");
+  *n = g->n_params;
+  return POB_OK;
+}
+
+int pob_gru_forward(const pob_gru *g, int B, const float *x, const float *theta, const float *reset, float *h_io,
+                    float *y, float *h_in_copy, void *stream) {
+  if (!g) return pob_fail_msg(POB_EINVAL, "gru is NULL");
+  if (B < 1) return pob_fail_msg(POB_EINVAL, "gru: batch size must be positive");
+  if (!x || !theta || !y) return pob_fail_msg(POB_EINVAL, "gru: NULL argument");
+  if (!h_io) return pob_fail_msg(POB_EINVAL, "gru: h_io is NULL");
+  GruDesc d = g->d;
+  gru_plan(d, false, d.p_rows);
+  const dim3 grid((unsigned)((B + MLP_ROWS - 1) / MLP_ROWS));
+  hipStream_t st = (hipStream_t)stream;
+  GRU_DISPATCH(k_gru_forward, g->cls_forward, d, B, x, theta, reset, h_io, y, h_in_copy)
+  return mlp_hip_check(hipGetLastError(), "k_gru_forward launch");
+}
+
+int pob_gru_policy_act(const pob_gru *g, int B, int total, int first, const float *obs, const float *theta,
+                       uint32_t *key_io, int deterministic, const float *reset, float *h_io, float *action, float *logp,
+                       float *raw, float *logits, float *obs_copy, float *h_in_copy, void *stream) {
+  if (!g) return pob_fail_msg(POB_EINVAL, "gru is NULL");
+  const int out = g->d.post[g->d.n_post - 1];
+  if (out & 1) return pob_fail_msg(POB_EINVAL, "policy: the last width must be even (loc and scale halves)");
+  if (B < 1 || first < 0 || total < 1 || (long long)first + B > total)
+    return pob_fail_msg(POB_EINVAL, "policy: bad shard (need first >= 0, B >= 1, first + B <= total)");
+  if ((long long)total * (out >> 1) >= 4294967295LL) return pob_fail_msg(POB_EINVAL, "policy: too many action elements");
+  if (!obs || !theta || !action) return pob_fail_msg(POB_EINVAL, "policy: NULL argument");
+  if (!h_io) return pob_fail_msg(POB_EINVAL, "policy: h_io is NULL");
+  if (!deterministic && !key_io) return pob_fail_msg(POB_EINVAL, "policy: key is NULL");
+  GruDesc d = g->d;
+  gru_plan(d, true, d.p_rows);
+  const dim3 grid((unsigned)((B + MLP_ROWS - 1) / MLP_ROWS));
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t *key = key_io;
+  GRU_DISPATCH(k_gru_policy_act, g->cls_actor, d, B, total, first, obs, theta, key, deterministic, reset, h_io, action,
+               logp, raw, logits, obs_copy, h_in_copy)
+  if (!deterministic) hipLaunchKernelGGL(k_mlp_advance_key, dim3(1), dim3(1), 0, st, key_io);
+  return mlp_hip_check(hipGetLastError(), "k_gru_policy_act launch");
 }
 
 }  // extern "C"

@@ -60,6 +60,7 @@ EXPORTS = (
     "pob_random_split", "pob_random_split_batch", "pob_random_uniform", "pob_random_actions", "pob_obs_gather",
     "pob_env_set_obs_mask",
     "pob_mlp_create", "pob_mlp_destroy", "pob_mlp_param_count", "pob_mlp_forward", "pob_policy_act",
+    "pob_gru_create", "pob_gru_destroy", "pob_gru_param_count", "pob_gru_forward", "pob_gru_policy_act",
 )
 
 
@@ -104,10 +105,18 @@ def _load():
     lib.pob_mlp_forward.argtypes = [_VP, C.c_int, _VP, _VP, _VP, _VP]
     lib.pob_policy_act.argtypes = [_VP, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int, _VP, _VP, _VP, _VP,
                                    _VP, _VP]
+    lib.pob_gru_create.argtypes = [C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int,
+                                   C.POINTER(_VP)]
+    lib.pob_gru_destroy.argtypes = [_VP]
+    lib.pob_gru_destroy.restype = None
+    lib.pob_gru_param_count.argtypes = [_VP, C.POINTER(C.c_longlong)]
+    lib.pob_gru_forward.argtypes = [_VP, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, _VP]
+    lib.pob_gru_policy_act.argtypes = [_VP, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int, _VP, _VP, _VP, _VP,
+                                       _VP, _VP, _VP, _VP, _VP]
     if lib.pob_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {lib.pob_abi_version()} != {ABI_VERSION}; rebuild it")
     for name in EXPORTS:
-        if name not in ("pob_abi_version", "pob_last_error", "pob_env_destroy", "pob_mlp_destroy"):
+        if name not in ("pob_abi_version", "pob_last_error", "pob_env_destroy", "pob_mlp_destroy", "pob_gru_destroy"):
             getattr(lib, name).restype = C.c_int
     return lib
 

@@ -316,3 +316,71 @@ class ActorRollout:
         """Run the captured unroll (stream-ordered on torch's current stream)."""
         self.graph.replay()
         return self.state
+
+
+class RecurrentActorRollout:
+    """``ActorRollout`` for a ``training.networks.RecurrentTanhPolicy``: ``T`` env-steps in ONE
+    hipGraph, per step one ``pob_gru_policy_act`` launch (pre-MLP, GRU cell, post-MLP, head),
+    the key advance, the fused step kernel and the reward / done copies.  The hidden state
+    lives in ``policy.hidden`` and is carried in place; the kernel zeroes it where the last
+    step ended an episode: at step t its ``reset`` input is ``done[t - 1]``, the trajectory
+    row already on the device, and at t = 0 it is ``policy.reset``, into which the graph's last
+    node copies ``done[T - 1]`` -- so state and episode boundaries carry across replays with
+    no host work.
+
+        roll = RecurrentActorRollout(env, state, policy, steps=T)
+        roll.replay()
+        roll.hidden[t]     # (B, H) the post-reset state step t started from (BPTT restarts here)
+        roll.obs[t], roll.actions[t], roll.logp[t], roll.raw[t], roll.reward[t], roll.done[t]
+
+    ``masked=True`` acts on ``state.info["obs_masked"]`` (the ``obs_mask=`` columns the step
+    kernel writes) instead of ``state.obs``; ``roll.obs`` then holds those columns.
+    Single-kind ``create(...)`` chains only."""
+
+    def __init__(self, env, state, policy, steps: int, masked: bool = False):
+        from .training.networks import RecurrentTanhPolicy
+        if steps <= 0:
+            raise ValueError("steps must be positive")
+        if not isinstance(policy, RecurrentTanhPolicy):
+            raise TypeError("policy must be a training.networks.RecurrentTanhPolicy")
+        if isinstance(state, (list, tuple)):
+            raise NotImplementedError("RecurrentActorRollout unrolls a single-kind create(...) env, not a MixedEnv")
+        if masked and "obs_masked" not in state.info:
+            raise ValueError("masked=True needs an env created with obs_mask=...")
+        self.masked = bool(masked)
+        obs = self._obs_of(state)
+        if not (obs.is_cuda and obs.dtype == torch.float32 and obs.dim() == 2):
+            raise ValueError("the observation must be a float32 (B, D) device tensor")
+        B, D = int(obs.shape[0]), int(obs.shape[1])
+        A, H = env.action_size, policy.hidden_size
+        if policy.action_size != A or policy.obs_size != D:
+            raise ValueError(f"the policy maps {policy.obs_size} -> {policy.action_size}, the env {D} -> {A}")
+        self.env, self.state, self.policy, self.steps = env, state, policy, int(steps)
+        dev, T = obs.device, self.steps
+        policy._buffers(B)  # hidden and reset exist before the capture
+        self.obs = torch.empty((T, B, D), dtype=torch.float32, device=dev)
+        self.actions = torch.empty((T, B, A), dtype=torch.float32, device=dev)
+        self.raw = torch.empty((T, B, A), dtype=torch.float32, device=dev)
+        self.logp = torch.zeros((T, B), dtype=torch.float32, device=dev)
+        self.hidden = torch.empty((T, B, H), dtype=torch.float32, device=dev)
+        self.reward = torch.empty((T, B), dtype=torch.float32, device=dev)
+        self.done = torch.empty((T, B), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.graph = torch.cuda.CUDAGraph()
+        with no_gc(), torch.cuda.graph(self.graph):
+            for t in range(T):
+                policy.act_into(self._obs_of(self.state), self.actions[t], self.logp[t], self.raw[t], None, self.obs[t],
+                                self.hidden[t], policy.reset if t == 0 else self.done[t - 1])
+                self.state = env.step_(self.state, self.actions[t])
+                self.reward[t].copy_(self.state.reward)
+                self.done[t].copy_(self.state.aux["done"] if "done" in self.state.aux else self.state.done)
+            policy.reset.copy_(self.done[T - 1])
+        _release_deferred()
+
+    def _obs_of(self, state):
+        return state.info["obs_masked"] if self.masked else state.obs
+
+    def replay(self):
+        """Run the captured unroll (stream-ordered on torch's current stream)."""
+        self.graph.replay()
+        return self.state

@@ -10,6 +10,10 @@ same network in plain torch ops otherwise (autograd for the learner, and the CPU
 (``pob_policy_act``), capture-safe, so it drops into ``rollout.PolicyRollout`` and is what
 ``rollout.ActorRollout`` unrolls.  Formulas, layouts and what is pinned: DESIGN.md "Policy
 networks".
+
+``make_recurrent_model`` / ``RecurrentTanhPolicy`` are the recurrent counterparts (pre-MLP ->
+GRU cell -> post-MLP, ``pob_gru_forward`` / ``pob_gru_policy_act``, the hidden state carried on
+the device), unrolled by ``rollout.RecurrentActorRollout``: DESIGN.md "Recurrent actor".
 """
 from __future__ import annotations
 
@@ -212,6 +216,241 @@ def make_models(policy_params_size: int, obs_size: int) -> Tuple[FeedForwardMode
     """The reference's PPO pair: policy [32] * 4 + [policy_params_size], value [256] * 5 + [1]."""
     return (make_model([32, 32, 32, 32, policy_params_size], obs_size),
             make_model([256, 256, 256, 256, 256, 1], obs_size))
+
+
+# ---- the recurrent actor (DESIGN.md "Recurrent actor"): pre-MLP -> GRU cell -> post-MLP
+MAX_HIDDEN, MAX_PRE, MAX_POST = 128, 3, 4
+
+
+class GRUHandle:
+    """A ``pob_gru`` (shape and activation only: host memory, no HIP call to make or free)."""
+
+    def __init__(self, pre_sizes: Sequence[int], hidden: int, post_sizes: Sequence[int], activation: int):
+        self.pre_sizes = [int(s) for s in pre_sizes]  # [obs width, *pre-MLP widths]
+        self.post_sizes = [int(s) for s in post_sizes]
+        self.hidden = int(hidden)
+        if not self.pre_sizes:
+            raise ValueError("gru: pre_sizes must start with the observation width")
+        pre = (C.c_int * len(self.pre_sizes))(*self.pre_sizes)
+        post = (C.c_int * max(1, len(self.post_sizes)))(*self.post_sizes)
+        h = C.c_void_p()
+        check(lib.pob_gru_create(len(self.pre_sizes) - 1, pre, self.hidden, len(self.post_sizes), post, int(activation),
+                                 C.byref(h)))
+        self._h = h
+        n = C.c_longlong()
+        check(lib.pob_gru_param_count(h, C.byref(n)))
+        self.param_count = int(n.value)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            lib.pob_gru_destroy(h)
+
+
+def _gru_layout(pre_sizes, hidden, post_sizes):
+    """``[(path, n_in, n_out)]`` of the weight matrices in ``theta`` order (each followed by its
+    bias of n_out entries); path = ("pre_i",), ("gru", "rz" | "xn" | "hn") or ("post_i",)."""
+    I, H = pre_sizes[-1], hidden
+    out = [((f"pre_{i}",), a, b) for i, (a, b) in enumerate(zip(pre_sizes[:-1], pre_sizes[1:]))]
+    out += [(("gru", "rz"), I + H, 2 * H), (("gru", "xn"), I, H), (("gru", "hn"), H, H)]
+    widths = [H] + list(post_sizes)
+    out += [((f"post_{i}",), a, b) for i, (a, b) in enumerate(zip(widths[:-1], widths[1:]))]
+    return out
+
+
+class RecurrentParams(dict):
+    """``{"pre_i": {kernel, bias}, "gru": {"rz" | "xn" | "hn": {kernel, bias}}, "post_i": {kernel,
+    bias}}`` whose tensors are views into the flat ``theta``."""
+
+    def __init__(self, theta: torch.Tensor, pre_sizes, hidden, post_sizes):
+        super().__init__()
+        self.theta = theta
+        self.pre_sizes, self.hidden, self.post_sizes = list(pre_sizes), int(hidden), list(post_sizes)
+        off = 0
+        for path, n_in, n_out in _gru_layout(self.pre_sizes, self.hidden, self.post_sizes):
+            kernel = theta[off:off + n_in * n_out].view(n_in, n_out)
+            off += n_in * n_out
+            leaf = {"kernel": kernel, "bias": theta[off:off + n_out]}
+            off += n_out
+            if len(path) == 1:
+                self[path[0]] = leaf
+            else:
+                self.setdefault(path[0], {})[path[1]] = leaf
+        if off != theta.numel():
+            raise ValueError(f"theta has {theta.numel()} elements, the network {off}")
+
+    def to(self, device) -> "RecurrentParams":
+        return RecurrentParams(self.theta.detach().to(device).contiguous(), self.pre_sizes, self.hidden, self.post_sizes)
+
+
+@dataclasses.dataclass
+class RecurrentModel:
+    init: Any
+    apply: Any
+    initial_state: Any
+    pre_sizes: Optional[Tuple[int, ...]] = None   # (obs_size, *pre_sizes)
+    hidden_size: Optional[int] = None
+    post_sizes: Optional[Tuple[int, ...]] = None
+    activation: Optional[int] = None
+    gru: Optional[GRUHandle] = None
+
+
+def _recurrent_torch(pre, H, post, act, theta, x, h, reset):
+    """The recurrent network in torch ops on 2-D x (B, D), h (B, H)."""
+    fn, off = _TORCH_ACT[act], 0
+
+    def dense(v, n_in, n_out):
+        nonlocal off
+        W = theta[off:off + n_in * n_out].view(n_in, n_out)
+        off += n_in * n_out
+        b = theta[off:off + n_out]
+        off += n_out
+        return torch.addmm(b, v, W)
+
+    for n_in, n_out in zip(pre[:-1], pre[1:]):
+        x = fn(dense(x, n_in, n_out))
+    I = pre[-1]
+    if reset is not None:
+        h = torch.where(reset.reshape(-1, 1) != 0, torch.zeros_like(h), h)
+    rz = torch.sigmoid(dense(torch.cat([x, h], dim=-1), I + H, 2 * H))
+    r, z = rz[:, :H], rz[:, H:]
+    cx = dense(x, I, H)
+    ch = dense(h, H, H)
+    n = torch.tanh(cx + r * ch)
+    h_new = n + z * (h - n)
+    y, widths = h_new, [H] + list(post)
+    for i, (n_in, n_out) in enumerate(zip(widths[:-1], widths[1:])):
+        y = dense(y, n_in, n_out)
+        if i != len(post) - 1:
+            y = fn(y)
+    return y, h_new
+
+
+def make_recurrent_model(pre_sizes: Sequence[int], hidden_size: int, post_sizes: Sequence[int], obs_size: int,
+                         activation: Any = "swish") -> RecurrentModel:
+    """``obs_size -> pre_sizes (activation after every layer) -> GRU cell (hidden_size) ->
+    post_sizes (activation after all but the last)``.  ``model.init(key)`` returns
+    ``RecurrentParams``: one ``key, sub = split(key)`` per weight matrix in ``theta`` order (the
+    pre-MLP's, W_rz, W_xn, W_hn, the post-MLP's), each lecun-uniform on its ``in``, biases zero.
+    ``model.apply(params, x, h, reset=None) -> (y, h_new)``: x (B, obs_size), h (B, hidden_size),
+    reset (B,) (non-zero: the env starts from h = 0).  ``model.initial_state(B, device)``: zeros."""
+    pre = (int(obs_size),) + tuple(int(s) for s in pre_sizes)
+    post = tuple(int(s) for s in post_sizes)
+    H = int(hidden_size)
+    act = _activation_id(activation)
+    gru = GRUHandle(pre, H, post, act)  # ValueError names the limit that is exceeded
+    layout = _gru_layout(pre, H, post)
+
+    def init(key) -> RecurrentParams:
+        key = _key_words(key)
+        dev = key.device
+        parts = []
+        for _, n_in, n_out in layout:
+            lim = math.sqrt(3.0 / n_in)
+            if dev.type == "cuda":
+                from .. import jumpy
+                key, sub = jumpy.random_split(key)
+                w = jumpy.random_uniform(sub, (n_in * n_out,), -lim, lim)
+            else:
+                key, sub = _host_split(key)
+                w = _host_uniform(sub, n_in * n_out, -lim, lim)
+            parts += [w, torch.zeros(n_out, dtype=torch.float32, device=dev)]
+        return RecurrentParams(torch.cat(parts).contiguous(), pre, H, post)
+
+    def initial_state(B: int, device=None) -> torch.Tensor:
+        return torch.zeros((int(B), H), dtype=torch.float32, device=device)
+
+    def apply(params, x: torch.Tensor, h: torch.Tensor, reset: Optional[torch.Tensor] = None):
+        theta = params.theta
+        if theta.numel() != gru.param_count:
+            raise ValueError(f"theta has {theta.numel()} elements, the network {gru.param_count}")
+        if x.dim() != 2 or x.shape[1] != pre[0] or tuple(h.shape) != (x.shape[0], H):
+            raise ValueError(f"x must be (B, {pre[0]}) and h (B, {H})")
+        if reset is not None and tuple(reset.shape) != (x.shape[0],):
+            raise ValueError("reset must be (B,)")
+        need_grad = torch.is_grad_enabled() and (x.requires_grad or h.requires_grad or theta.requires_grad)
+        fused = (x.is_cuda and x.dtype == torch.float32 and theta.is_cuda and theta.dtype == torch.float32
+                 and theta.is_contiguous() and h.is_cuda and h.dtype == torch.float32 and not need_grad)
+        if not fused:
+            return _recurrent_torch(pre, H, post, act, theta, x, h, reset)
+        x2 = x.detach().contiguous()
+        h_new = h.detach().clone(memory_format=torch.contiguous_format)
+        rs = None if reset is None else reset.detach().to(torch.float32).contiguous()
+        y = torch.empty((x2.shape[0], post[-1]), dtype=torch.float32, device=x.device)
+        if x2.shape[0]:
+            check(lib.pob_gru_forward(gru.handle, x2.shape[0], ptr(x2), ptr(theta.detach()), ptr(rs), ptr(h_new), ptr(y),
+                                      None, _lib.stream_handle(x.device)))
+        return y, h_new
+
+    return RecurrentModel(init=init, apply=apply, initial_state=initial_state, pre_sizes=pre, hidden_size=H,
+                          post_sizes=post, activation=act, gru=gru)
+
+
+class RecurrentTanhPolicy:
+    """The recurrent counterpart of ``NormalTanhPolicy``: ``policy(obs) -> action`` is ONE
+    ``pob_gru_policy_act`` launch (pre-MLP, GRU cell, post-MLP, tanh-normal head) plus the one-
+    thread key advance.  The policy owns ``hidden`` (B, H), carried in place from call to call,
+    and ``reset`` (B,): where it is non-zero the env starts the next call from h = 0 (write the
+    env's ``done`` into it).  Both are allocated at first use and start as zeros; after that no
+    allocation, no host sync: capture-safe."""
+
+    def __init__(self, model: RecurrentModel, params: RecurrentParams, key, total: Optional[int] = None, first: int = 0,
+                 deterministic: bool = False):
+        if model.gru is None:
+            raise ValueError("model must come from make_recurrent_model")
+        if model.post_sizes[-1] % 2:
+            raise ValueError("the policy network's last width must be even (loc and scale halves)")
+        theta = params.theta
+        if not (theta.is_cuda and theta.dtype == torch.float32 and theta.is_contiguous()):
+            raise ValueError("params.theta must be a contiguous float32 CUDA tensor (params.to('cuda'))")
+        if theta.numel() != model.gru.param_count:
+            raise ValueError(f"theta has {theta.numel()} elements, the network {model.gru.param_count}")
+        self.model, self.params, self.theta = model, params, theta
+        self.obs_size, self.action_size = model.pre_sizes[0], model.post_sizes[-1] // 2
+        self.hidden_size = model.hidden_size
+        self.key = _key_words(key).to(theta.device).clone()
+        self.total, self.first = (None if total is None else int(total)), int(first)
+        self.deterministic = bool(deterministic)
+        self.action = self.logp = self.raw = self.hidden = self.reset = None
+
+    def _buffers(self, B: int):
+        if self.hidden is None or self.hidden.shape[0] != B:
+            dev = self.theta.device
+            self.action = torch.zeros((B, self.action_size), dtype=torch.float32, device=dev)
+            self.raw = torch.zeros((B, self.action_size), dtype=torch.float32, device=dev)
+            self.logp = torch.zeros((B,), dtype=torch.float32, device=dev)
+            self.hidden = torch.zeros((B, self.hidden_size), dtype=torch.float32, device=dev)
+            self.reset = torch.zeros((B,), dtype=torch.float32, device=dev)
+
+    def act_into(self, obs: torch.Tensor, action: torch.Tensor, logp=None, raw=None, logits=None, obs_copy=None,
+                 hidden_in=None, reset=None):
+        """One launch on caller buffers (contiguous float32 device tensors; None = skip).
+        ``hidden_in`` (B, H) receives the state the step started from, after the reset;
+        ``reset`` (B,) replaces ``self.reset`` for this call."""
+        if not (obs.is_cuda and obs.dtype == torch.float32 and obs.dim() == 2 and obs.shape[1] == self.obs_size
+                and obs.is_contiguous()):
+            raise ValueError(f"obs must be a contiguous float32 CUDA tensor (B, {self.obs_size})")
+        B, A, H = int(obs.shape[0]), self.action_size, self.hidden_size
+        self._buffers(B)
+        reset = self.reset if reset is None else reset
+        for t, shape in ((action, (B, A)), (logp, (B,)), (raw, (B, A)), (logits, (B, 2 * A)), (obs_copy, (B, self.obs_size)),
+                         (hidden_in, (B, H)), (reset, (B,))):
+            if t is not None and not (tuple(t.shape) == shape and t.dtype == torch.float32 and t.is_contiguous()
+                                      and t.device == obs.device):
+                raise ValueError(f"buffer must be a contiguous float32 tensor {shape} on {obs.device}")
+        total = B if self.total is None else self.total
+        check(lib.pob_gru_policy_act(self.model.gru.handle, B, total, self.first, ptr(obs), ptr(self.theta), ptr(self.key),
+                                     int(self.deterministic), ptr(reset), ptr(self.hidden), ptr(action), ptr(logp),
+                                     ptr(raw), ptr(logits), ptr(obs_copy), ptr(hidden_in), _lib.stream_handle(obs.device)))
+        return action
+
+    def __call__(self, obs: torch.Tensor) -> torch.Tensor:
+        self._buffers(int(obs.shape[0]))
+        return self.act_into(obs, self.action, self.logp, self.raw)
 
 
 class NormalTanhPolicy:

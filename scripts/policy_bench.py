@@ -12,6 +12,17 @@ replayed in turn (A, B, C, A, B, C, ..), the median replay time of each:
 Prints one JSON line: ms/step of each and the policy's share A - C and B - C.
 
     python scripts/policy_bench.py [--batch 65536] [--steps 20] [--rounds 15] [--out FILE]
+
+--recurrent runs the same three legs with the recurrent actor (GRU cell of --hidden features,
+no pre-MLP, one post layer of 2 A logits):
+
+  A  rollout.PolicyRollout with that network in torch ops (cat, addmm, sigmoid, tanh, where),
+     the hidden state carried and zeroed where the last step ended an episode
+  B  rollout.RecurrentActorRollout: ONE pob_gru_policy_act launch per step
+  C  rollout.GraphRollout on pre-drawn actions
+
+--masked creates the envs with the standard observability mask (30 of HH's 114 columns, fused
+into the step kernel) and both policies act on state.info["obs_masked"].
 """
 import argparse
 import json
@@ -43,6 +54,46 @@ class TorchNormalTanhPolicy:
         return torch.tanh(loc + scale * torch.randn_like(loc))
 
 
+class TorchRecurrentPolicy:
+    """The recurrent actor in torch ops on the same flat parameters (action only).  ``tap`` is
+    the env proxy below: it holds the State the last step returned and writes its done into
+    ``self.reset``."""
+
+    def __init__(self, model, params, B, action_size, masked):
+        self.model, self.theta, self.A, self.masked = model, params.theta, action_size, masked
+        self.hidden = torch.zeros((B, model.hidden_size), device=params.theta.device)
+        self.reset = torch.zeros((B,), device=params.theta.device)
+        self.tap = None
+
+    def __call__(self, obs):
+        from po_brax_amd.training.networks import _recurrent_torch
+        m = self.model
+        if self.masked:
+            obs = self.tap.state.info["obs_masked"]
+        y, h = _recurrent_torch(m.pre_sizes, m.hidden_size, m.post_sizes, m.activation, self.theta, obs, self.hidden,
+                                self.reset)
+        self.hidden.copy_(h)
+        loc, s = y[:, :self.A], y[:, self.A:]
+        scale = torch.nn.functional.softplus(s) + 0.001
+        return torch.tanh(loc + scale * torch.randn_like(loc))
+
+
+class DoneTap:
+    """An env whose step_ also copies the step's done into ``policy.reset`` (leg A's episode
+    boundaries) and remembers the returned State."""
+
+    def __init__(self, env, state, policy):
+        self.env, self.state, self.policy = env, state, policy
+        self.action_size = env.action_size
+        policy.tap = self
+
+    def step_(self, state, action):
+        s = self.env.step_(state, action)
+        self.policy.reset.copy_(s.aux["done"] if "done" in s.aux else s.done)
+        self.state = s
+        return s
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--env", default="ant_heavenhell")
@@ -51,22 +102,41 @@ def main():
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--recurrent", action="store_true")
+    ap.add_argument("--masked", action="store_true")
+    ap.add_argument("--hidden", type=int, default=64)
     args = ap.parse_args()
 
     from po_brax_amd import envs, jumpy
-    from po_brax_amd.rollout import ActorRollout, GraphRollout, PolicyRollout
+    from po_brax_amd.rollout import ActorRollout, GraphRollout, PolicyRollout, RecurrentActorRollout
     from po_brax_amd.training import networks
 
     B, T = args.batch, args.steps
     keys = jumpy.random_split(jumpy.random_prngkey(0), B + 1)[1:]
-    es = [envs.create(args.env, batch_size=B) for _ in range(3)]
+    mask = None
+    if args.masked:
+        if not args.recurrent:
+            ap.error("--masked goes with --recurrent")
+        from po_brax_amd import standard_observability_masks as M
+        mask = M.po_env_mask(args.env, cfrc=False)
+    es = [envs.create(args.env, batch_size=B, obs_mask=mask) for _ in range(3)]
     ss = [e.reset(keys) for e in es]
     A, D = es[0].action_size, es[0].observation_size
-    model = networks.make_models(2 * A, D)[0]
-    params = model.init(jumpy.random_prngkey(1))
-    with torch.no_grad():
-        roll_a = PolicyRollout(es[0], ss[0], TorchNormalTanhPolicy(params, A), T)
-    roll_b = ActorRollout(es[1], ss[1], networks.NormalTanhPolicy(model, params, jumpy.random_prngkey(2)), T)
+    if args.recurrent:
+        D = es[0].masked_observation_size if args.masked else D
+        model = networks.make_recurrent_model([], args.hidden, [2 * A], D)
+        params = model.init(jumpy.random_prngkey(1))
+        torch_policy = TorchRecurrentPolicy(model, params, B, A, args.masked)
+        with torch.no_grad():
+            roll_a = PolicyRollout(DoneTap(es[0], ss[0], torch_policy), ss[0], torch_policy, T)
+        roll_b = RecurrentActorRollout(es[1], ss[1], networks.RecurrentTanhPolicy(model, params, jumpy.random_prngkey(2)),
+                                       T, masked=args.masked)
+    else:
+        model = networks.make_models(2 * A, D)[0]
+        params = model.init(jumpy.random_prngkey(1))
+        with torch.no_grad():
+            roll_a = PolicyRollout(es[0], ss[0], TorchNormalTanhPolicy(params, A), T)
+        roll_b = ActorRollout(es[1], ss[1], networks.NormalTanhPolicy(model, params, jumpy.random_prngkey(2)), T)
     acts = torch.rand((T, B, A), device="cuda") * 2 - 1
     roll_c = GraphRollout(es[2], ss[2], acts, warmup=True)
     rolls = {"A": roll_a, "B": roll_b, "C": roll_c}
@@ -88,7 +158,8 @@ def main():
             ms[k].append(timed(r))
     med = {k: statistics.median(v) for k, v in ms.items()}
     res = {
-        "bench": "policy_bench", "env": args.env, "batch": B, "steps": T, "rounds": args.rounds,
+        "bench": "policy_bench", "recurrent": args.recurrent, "masked": args.masked,
+        "obs_width": D, "hidden": args.hidden if args.recurrent else None, "env": args.env, "batch": B, "steps": T, "rounds": args.rounds,
         "device": torch.cuda.get_device_name(0),
         "A_policy_rollout_torch_ms_per_step": round(med["A"], 5),
         "B_actor_rollout_ms_per_step": round(med["B"], 5),
