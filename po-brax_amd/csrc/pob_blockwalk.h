@@ -59,6 +59,10 @@ POB_BW_D void bw_prefix_step(const uint64_t m, const int lane, const int b, int 
   tot += __builtin_popcountll(m) << b;
 }
 #define QBW_PREFIX_BITS 7  // (QBW_LANE_MAX = 64 needs bits 0 .. 6)
+// a wave none of whose lanes holds 4 items or more needs steps 0 and 1 only (the ballots of the
+// higher bits are empty: their steps add nothing)
+#define QBW_PREFIX_SHORT_BITS 2
+POB_BW_D constexpr bool bw_prefix_needs_all(const int count) { return count >= (1 << QBW_PREFIX_SHORT_BITS); }
 
 // the lane's next item in walk order -- the lowest set bit of the first slot with one -- taken
 // out of M; false when the lane has none left
@@ -117,3 +121,37 @@ POB_BW_D void bw_body_ranges(const int base, const int n0, const int n1, const i
   c[2] = ovf ? c[0] : c[1] + 2 * n1;
   c[3] = ovf ? c[0] : c[2] + 2 * n2;
 }
+
+// The torso's items once per lane quad (pob_quad.h POB_QUAD_TORSO_ONCE): the four lanes of a
+// quad (lanes 4 e .. 4 e + 3 of a wave: one env) hold bit-identical replicas of the torso, so
+// only the quad's lane 0 counts and publishes the torso's items -- n0 of them, from its own
+// base base0 on -- and all four lanes apply the torso's contacts from those slots.
+POB_BW_D constexpr bool bw_quad_lead(const int lane) { return (lane & 3) == 0; }
+// the torso items a lane publishes and counts into its lane count
+POB_BW_D constexpr int bw_quad_torso_count(const int lane, const int n0) { return bw_quad_lead(lane) ? n0 : 0; }
+// The ranges of a lane: the torso's contact slots [c[0], c[1]) -- the quad's lane-0 slots, base0
+// that lane's prefix base -- and the lane's own Aux and lower-leg slots [c[2], c[3]) and
+// [c[3], c[4]), which start at the lane's own base (behind the torso's in the quad's lane 0).
+// All empty in an overflowing block.
+POB_BW_D void bw_quad_ranges(const int lane, const int base0, const int n0, const int base, const int n1, const int n2,
+                             const bool ovf, int (&c)[5]) {
+  c[0] = 2 * base0;
+  c[1] = ovf ? c[0] : c[0] + 2 * n0;
+  c[2] = 2 * (base + bw_quad_torso_count(lane, n0));
+  c[3] = ovf ? c[2] : c[2] + 2 * n1;
+  c[4] = ovf ? c[2] : c[3] + 2 * n2;
+}
+
+// One hit scan per collide substep (pob_quad.h POB_QUAD_HIT_MASK): after the evaluation a lane
+// reads the two dist words of each item of a body once and keeps "triangle t of the body's item
+// i holds a contact" as bit 2 i + t of a 32-bit mask; both apply passes walk the mask's set bits
+// (contact slot = the body's first slot + the bit's number), lowest first: the walk order.  A
+// body with more than QBW_HIT_ITEMS items (a launch may lower it) does not fit: its wave
+// publishes an overflowing count (bw_hit_count), so the block applies nothing and goes to the
+// fix-up launch.
+#define QBW_HIT_ITEMS 16
+POB_BW_D constexpr uint32_t bw_hit_bits(const bool h0, const bool h1, const int i) {
+  return ((h0 ? 1u : 0u) | (h1 ? 2u : 0u)) << (2 * i);
+}
+// the wave's count as published: wide = some lane of the wave holds a body past the mask's width
+POB_BW_D constexpr int bw_hit_count(const int tot, const bool wide) { return wide && tot <= QBW_WCAP ? QBW_WCAP + 1 : tot; }

@@ -66,7 +66,12 @@ struct pob_env {
 // ordinary states; eight internal flags bits, 0 = the full capacity)
 #define POB_F_INT_BWCAP_SHIFT 20
 #define POB_F_INT_BWCAP_MASK (0xFFu << POB_F_INT_BWCAP_SHIFT)
-#define POB_F_INTERNAL (POB_F_STAGED | POB_F_INT_FORCE_FIXUP | POB_F_INT_BWCAP_MASK)
+// (test hook: POB_QUAD_HIT_WIDTH=n lowers the items of a body that fit a lane's hit mask to n
+// (1 .. 7; QBW_HIT_ITEMS otherwise), so the hand-over of a block with a wider body to the fix-up
+// launch runs at states a test can build; three internal flags bits, 0 = the full width)
+#define POB_F_INT_HITW_SHIFT 17
+#define POB_F_INT_HITW_MASK (0x7u << POB_F_INT_HITW_SHIFT)
+#define POB_F_INTERNAL (POB_F_STAGED | POB_F_INT_FORCE_FIXUP | POB_F_INT_BWCAP_MASK | POB_F_INT_HITW_MASK)
 #define POB_F_PUBLIC (POB_F_EPISODE | POB_F_AUTORESET | POB_F_ZERO_STEPS_ON_DONE)
 
 // ---------------------------------------------------------------------------- state
@@ -990,8 +995,9 @@ POB_D void step_quad_body(csys_t *Sp, const int B, const StatePtrs &in, const fl
       // barriers in each collide substep, qwalls_detect_block) and only then leaves -- a wave past
       // the batch with nothing stored, an overflowed block (block-uniform) to the fix-up launch
       const int capf = (int)((flags & POB_F_INT_BWCAP_MASK) >> POB_F_INT_BWCAP_SHIFT);
+      const int hitf = (int)((flags & POB_F_INT_HITW_MASK) >> POB_F_INT_HITW_SHIFT);
       QBlock blk{lds + QPOOL_OFF, __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), 0,
-                 capf != 0 ? capf : QBW_CAP, dead, false};
+                 capf != 0 ? capf : QBW_CAP, hitf != 0 ? hitf : QBW_HIT_ITEMS, dead, false};
 #pragma nounroll
       for (int it = 0; it < 2 * iters; ++it) {
 #if POB_QUAD_PRIO == 1
@@ -2967,6 +2973,11 @@ static uint32_t quad_block_cap() {
   const int n = f ? atoi(f) : 0;
   return n >= 1 && n < QBW_CAP ? (uint32_t)n << POB_F_INT_BWCAP_SHIFT : 0u;
 }
+static uint32_t quad_hit_width() {
+  const char *f = getenv("POB_QUAD_HIT_WIDTH");
+  const int n = f ? atoi(f) : 0;
+  return n >= 1 && n <= 7 ? (uint32_t)n << POB_F_INT_HITW_SHIFT : 0u;
+}
 template <typename QT>
 static void launch_step_quad(int kind, bool legacy, int n_cu, hipStream_t st, const void *sp, int B,
                              const StatePtrs &pi, const float *act, const StatePtrs &po, uint32_t flags, int L) {
@@ -2994,7 +3005,7 @@ static void launch_step_quad(int kind, bool legacy, int n_cu, hipStream_t st, co
   flags |= split ? quad_force_fixup() : 0u;
   // 256-thread blocks of HH / TAG: the fast launch's block-cooperative wall walk
   const bool coop = split && bs == 256 && (kind == POB_HEAVENHELL || kind == POB_TAG);
-  flags |= coop ? quad_block_cap() : 0u;
+  flags |= coop ? quad_block_cap() | quad_hit_width() : 0u;
   switch (kind) {
     case POB_HEAVENHELL:
       if (split) {

@@ -180,8 +180,13 @@ struct QWalls {
   int nct;                // wall contacts of the position pass
   float c[6 * QK];        // the first QK: body, tau, n, dist (the re-walk builds, OVF)
   float seg[6 * QNB];     // nct > QK only: the segments a, b of the three bodies
-  int cb[QNB + 1];        // the block-cooperative walk only: body l's contact slots [cb[l], cb[l + 1]) (bw_body_ranges)
+  // the block-cooperative walk only: the torso's contact slots [cb[0], cb[1]) and the lane's own
+  // Aux and lower-leg slots [cb[2], cb[3]), [cb[3], cb[4]) (bw_quad_ranges; qcb_lo), and per body
+  // the slots that hold a contact (bw_hit_bits, POB_QUAD_HIT_MASK)
+  int cb[QNB + 2];
+  uint32_t hm[QNB];
 };
+POB_D constexpr int qcb_lo(const int l) { return l == 0 ? 0 : l + 1; }  // body l's slots: [cb[qcb_lo(l)], cb[qcb_lo(l) + 1])
 #ifndef POB_QUAD_WAVE_WALK
 #define POB_QUAD_WAVE_WALK 1  // 1: the wave-cooperative face walk (pob_mesh.h mesh_wave_walk)
 #endif
@@ -538,7 +543,10 @@ POB_D void qwalls_detect(csys_t *Sp, const float *LT, const float *WT, const QBo
 // Publish and apply run body by body: a lane's walk order is "slot, then bit", so its records
 // and contact slots are grouped torso, Aux, lower leg (bw_body_ranges), and a loop per body with
 // the body a compile-time value needs no selects over the lane's three bodies (DESIGN.md §4
-// "Round-8 findings").
+// "Round-8 findings").  The torso is the same body in the four lanes of a quad: its items are
+// published once, by the quad's lane 0, and its contact slots read by all four; and the owners
+// look for the slots that hold a contact once, after barrier 2, not once in each pass (the
+// switches below; DESIGN.md §4 "Round-9 findings").
 // Two barriers per collide substep suffice: between barrier 2 and the next barrier 1 a wave
 // reads (apply) and writes (the next publish) only its OWN segment, and the others touch that
 // segment only between a barrier 1 and the barrier 2 after it (evaluation: they read its
@@ -551,11 +559,29 @@ POB_D void qwalls_detect(csys_t *Sp, const float *LT, const float *WT, const QBo
 // executes both barriers whatever its items, its lanes past the batch, its overflow state --
 // a wave past the batch (dead) publishes no items and still evaluates its rounds; an overflow
 // (block-uniform: every wave derives it from the same four counts) only empties the deal.
+// Three A/B switches (DESIGN.md §4 "Round-9 findings"), each 1 = on:
+//   POB_QUAD_TORSO_ONCE    the torso's items counted and published by the quad's lane 0 alone
+//                          (its four lanes hold the same torso) and applied by all four from that
+//                          lane's slots (bw_quad_ranges) -- 0: every lane publishes its replica's;
+//   POB_QUAD_HIT_MASK      one scan of the contact slots per collide substep into a hit mask per
+//                          body that both passes walk (bw_hit_bits) -- 0: each pass skips the
+//                          no-contact slots on its own (qblock_next_hit);
+//   POB_QUAD_PREFIX_SHORT  the prefix's steps 2 .. 6 only in a wave with a lane of 4 items or more.
+#ifndef POB_QUAD_TORSO_ONCE
+#define POB_QUAD_TORSO_ONCE 1
+#endif
+#ifndef POB_QUAD_HIT_MASK
+#define POB_QUAD_HIT_MASK 1
+#endif
+#ifndef POB_QUAD_PREFIX_SHORT
+#define POB_QUAD_PREFIX_SHORT 1
+#endif
 struct QBlock {
   float *xch;  // segment 0 (the block's LDS + QPOOL_OFF; segment w at + w * 64 QL_FLOATS)
   int w;       // the wave's number in the block
   int sub;     // collide substeps done
   int cap;     // the block's item capacity (QBW_CAP; lower: the POB_QUAD_BLOCK_CAP test hook)
+  int hitw;    // a body's items that fit the hit mask (QBW_HIT_ITEMS; lower: the POB_QUAD_HIT_WIDTH test hook)
   bool dead;   // a wave past the batch
   bool ovf;    // the block overflowed in some substep (block-uniform)
 };
@@ -583,13 +609,39 @@ POB_D void qwalls_detect_block(csys_t *Sp, const float *LT, const float *WT, con
   // publish: the lanes' items in lane order, each lane's in walk order (slot, then bit) -- body
   // by body with the slot a compile-time value: the record is the cull's segment of that body
   float *own = L.pool();
+#if POB_QUAD_TORSO_ONCE
+  {
+    // the torso's items once per quad: its mask from the quad's lane 0 (the four replicas' masks
+    // are the same set -- a wall outside a lane's broadphase has every torso face culled -- and the
+    // broadcast keeps the four lanes from ever disagreeing), published and counted by that lane alone
+    const uint32_t lo = (uint32_t)__float_as_int(quad_bcast<0>(__int_as_float((int)(uint32_t)M[0])));
+    const uint32_t hi = (uint32_t)__float_as_int(quad_bcast<0>(__int_as_float((int)(uint32_t)(M[0] >> 32))));
+    M[0] = ((uint64_t)hi << 32) | lo;
+  }
+  const int n0 = __builtin_popcountll(M[0]);  // the quad's torso items
+  if (!bw_quad_lead(L.t)) M[0] = 0ull;
+#else
+  const int n0 = __builtin_popcountll(M[0]);
+#endif
+  const int n1 = __builtin_popcountll(M[1]), n2 = __builtin_popcountll(M[2]);
   const int nl = bw_lane_count(M[0], M[1], M[2]);
-  int nb[QNB];
-#pragma unroll
-  for (int l = 0; l < QNB; ++l) nb[l] = __builtin_popcountll(M[l]);
   int base = 0, tot = 0;
+#if POB_QUAD_PREFIX_SHORT
+#pragma unroll
+  for (int bit = 0; bit < QBW_PREFIX_SHORT_BITS; ++bit) bw_prefix_step(__ballot(((nl >> bit) & 1) != 0), L.t, bit, base, tot);
+  if (__any(bw_prefix_needs_all(nl))) {  // (wave-uniform; rare: a lane seldom holds more than 3 items)
+#pragma unroll
+    for (int bit = QBW_PREFIX_SHORT_BITS; bit < QBW_PREFIX_BITS; ++bit)
+      bw_prefix_step(__ballot(((nl >> bit) & 1) != 0), L.t, bit, base, tot);
+  }
+#else
 #pragma unroll
   for (int bit = 0; bit < QBW_PREFIX_BITS; ++bit) bw_prefix_step(__ballot(((nl >> bit) & 1) != 0), L.t, bit, base, tot);
+#endif
+#if POB_QUAD_HIT_MASK
+  // a body past the hit mask's width: the wave publishes an overflowing count (the fix-up launch)
+  tot = bw_hit_count(tot, __any((n0 > blk.hitw) | (n1 > blk.hitw) | (n2 > blk.hitw)) != 0);
+#endif
   {
     int at = base;
 #pragma unroll
@@ -616,11 +668,11 @@ POB_D void qwalls_detect_block(csys_t *Sp, const float *LT, const float *WT, con
   qblock_barrier();  // BARRIER 1: every wave's records and count are in LDS
   const int ws_f = QL_FLOATS * 64;
   // (the four counts: the same words in every lane and wave -- held as scalars)
-  const int n0 = __builtin_amdgcn_readfirstlane(__float_as_int(blk.xch[bw_count_off()]));
-  const int n1 = __builtin_amdgcn_readfirstlane(__float_as_int(blk.xch[ws_f + bw_count_off()]));
-  const int n2 = __builtin_amdgcn_readfirstlane(__float_as_int(blk.xch[2 * ws_f + bw_count_off()]));
-  const int n3 = __builtin_amdgcn_readfirstlane(__float_as_int(blk.xch[3 * ws_f + bw_count_off()]));
-  const BwDeal d = bw_deal(n0, n1, n2, n3, blk.cap);
+  const int w0 = __builtin_amdgcn_readfirstlane(__float_as_int(blk.xch[bw_count_off()]));
+  const int w1 = __builtin_amdgcn_readfirstlane(__float_as_int(blk.xch[ws_f + bw_count_off()]));
+  const int w2 = __builtin_amdgcn_readfirstlane(__float_as_int(blk.xch[2 * ws_f + bw_count_off()]));
+  const int w3 = __builtin_amdgcn_readfirstlane(__float_as_int(blk.xch[3 * ws_f + bw_count_off()]));
+  const BwDeal d = bw_deal(w0, w1, w2, w3, blk.cap);
   blk.ovf = blk.ovf | d.ovf;
   {
     GuardBranch g;
@@ -628,15 +680,45 @@ POB_D void qwalls_detect_block(csys_t *Sp, const float *LT, const float *WT, con
   }
   qblock_barrier();  // BARRIER 2: every contact slot of the deal is written
   ++blk.sub;
-  bw_body_ranges(base, nb[0], nb[1], nb[2], d.ovf, ws.cb);
-#ifdef POB_EXP_NO_APPLY
-  {  // timing experiment only: the walk runs, its contacts are not applied
-    int z = ws.cb[0];
-    asm volatile("" : "+v"(z));
-    ws.cb[1] = z; ws.cb[2] = z; ws.cb[3] = z;
+#if POB_QUAD_TORSO_ONCE
+  // (all four lanes apply the torso's contacts from the quad's lane-0 slots: the same words in
+  // the same order, so the replicas stay bit-identical)
+  const int base0 = __float_as_int(quad_bcast<0>(__int_as_float(base)));
+  bw_quad_ranges(L.t, base0, n0, base, n1, n2, d.ovf, ws.cb);
+#else
+  {
+    int c[QNB + 1];
+    bw_body_ranges(base, n0, n1, n2, d.ovf, c);
+    ws.cb[0] = c[0]; ws.cb[1] = c[1]; ws.cb[2] = c[1]; ws.cb[3] = c[2]; ws.cb[4] = c[3];
   }
 #endif
-  ws.nct = ws.cb[QNB] - ws.cb[0];
+#ifdef POB_EXP_NO_APPLY
+  {  // timing experiment only: the walk runs, its contacts are not applied
+    int z = ws.cb[0], y = ws.cb[2];
+    asm volatile("" : "+v"(z), "+v"(y));
+    ws.cb[1] = z; ws.cb[3] = y; ws.cb[4] = y;
+  }
+#endif
+  ws.nct = (ws.cb[1] - ws.cb[0]) + (ws.cb[4] - ws.cb[2]);
+#if POB_QUAD_HIT_MASK
+  // the one hit scan of the substep: per body, the dist words of its items' two triangles (one
+  // ds_read2 per item, the reads independent of each other) into the hit mask both passes walk
+#pragma unroll
+  for (int l = 0; l < QNB; ++l) {
+    const int c0 = ws.cb[qcb_lo(l)], n = (ws.cb[qcb_lo(l) + 1] - c0) >> 1;  // (n <= blk.hitw <= QBW_HIT_ITEMS; 0 on overflow)
+    uint32_t hm = 0u;
+#pragma unroll 1
+    for (int i = 0; __any(i < n); ++i) {
+      if (i < n) {
+        const float *p = own + bw_con_off(c0 + 2 * i);
+        hm |= bw_hit_bits(__float_as_int(p[QBW_CON_DW - 1]) != QBW_NO_CONTACT,
+                          __float_as_int(p[2 * QBW_CON_DW - 1]) != QBW_NO_CONTACT, i);
+      }
+    }
+    ws.hm[l] = hm;
+  }
+  ws.nct = (int)(ws.hm[0] | ws.hm[1] | ws.hm[2]);  // (the passes ask only whether it is 0)
+#endif
 }
 
 // The lane's next contact slot in [c, c1) that holds a contact (c1: none left).  The owners
@@ -784,25 +866,43 @@ POB_D void qcontacts_position(csys_t *Sp, const float *LT, const float *WT, QBod
     const float *sg = L.pool();
 #pragma unroll
     for (int l = 0; l < QNB; ++l) {
-      const int c1 = ws.cb[l + 1];
-      if (!__any(ws.cb[l] < c1)) continue;
+#if POB_QUAD_HIT_MASK
+      uint32_t hm = ws.hm[l];
+      if (!__any(hm != 0u)) continue;
+#else
+      const int c1 = ws.cb[qcb_lo(l) + 1];
+      if (!__any(ws.cb[qcb_lo(l)] < c1)) continue;
+#endif
       const v3 px = L.get3(l, QF_PX);
       const q4 pq = L.get4(l, QF_PQ);
       // (the capsule end rotated once per body: qseg_point's operands)
       const v3 rv = l == 0 ? V(0.0f, 0.0f, 0.0f) : qrot_xy(qcap_end(S, LT, l, 0), b.q[l]);
       const float r = q_cap_r(S, LT, l), im = q_inv_mass(S, LT, l);
-      int c = qblock_next_hit(sg, ws.cb[l], c1);
+      const auto apply = [&](const float *p) {
+        const float tau = p[0], dist = p[4];
+        const v3 pe = l == 0 ? b.x[0] : vfma(rv, tau, b.x[l]);
+        owall_position(g, SC, r - dist, pe, V(p[1], p[2], p[3]), 1e-6f + dist, im, b.x[l], b.q[l], pq, px, DX[l], DA[l]);
+      };
+#if POB_QUAD_HIT_MASK
+      // (the hit mask's set bits, lowest first: the lane's contacts in walk order)
+#pragma unroll 1
+      while (__any(hm != 0u)) {
+        if (hm != 0u) {
+          apply(sg + bw_con_off(ws.cb[qcb_lo(l)] + __builtin_ctz(hm)));
+          hm &= hm - 1u;
+        }
+      }
+#else
+      int c = qblock_next_hit(sg, ws.cb[qcb_lo(l)], c1);
 #pragma unroll 1
       while (__any(c < c1)) {
         if (c < c1) {
-          const float *p = sg + bw_con_off(c);
-          const float tau = p[0], dist = p[4];
-          const v3 pe = l == 0 ? b.x[0] : vfma(rv, tau, b.x[l]);
-          owall_position(g, SC, r - dist, pe, V(p[1], p[2], p[3]), 1e-6f + dist, im, b.x[l], b.q[l], pq, px, DX[l], DA[l]);
+          apply(sg + bw_con_off(c));
           ++c;
         }
         c = qblock_next_hit(sg, c, c1);
       }
+#endif
     }
     return;
   }
@@ -891,23 +991,40 @@ POB_D void qcontacts_velocity(csys_t *Sp, const float *LT, const float *WT, QBod
     const float *sg = L.pool();  // (body by body, as the position pass)
 #pragma unroll
     for (int l = 0; l < QNB; ++l) {
-      const int c1 = ws.cb[l + 1];
-      if (!__any(ws.cb[l] < c1)) continue;
+#if POB_QUAD_HIT_MASK
+      uint32_t hm = ws.hm[l];
+      if (!__any(hm != 0u)) continue;
+#else
+      const int c1 = ws.cb[qcb_lo(l) + 1];
+      if (!__any(ws.cb[qcb_lo(l)] < c1)) continue;
+#endif
       const v3 rv = l == 0 ? V(0.0f, 0.0f, 0.0f) : qrot_xy(qcap_end(S, LT, l, 0), b.q[l]);
       const float r = q_cap_r(S, LT, l), im = q_inv_mass(S, LT, l);
-      int c = qblock_next_hit(sg, ws.cb[l], c1);
+      const auto apply = [&](const float *p) {
+        const float tau = p[0], dist = p[4];
+        const v3 pe = l == 0 ? b.x[0] : vfma(rv, tau, b.x[l]);
+        ocontact_vel_pe(g, SC, false, r - dist, pe, V(p[1], p[2], p[3]), 1e-6f + dist, im, b.x[l], b.v[l], b.w[l], dV[l],
+                        dW[l]);
+      };
+#if POB_QUAD_HIT_MASK
+#pragma unroll 1
+      while (__any(hm != 0u)) {
+        if (hm != 0u) {
+          apply(sg + bw_con_off(ws.cb[qcb_lo(l)] + __builtin_ctz(hm)));
+          hm &= hm - 1u;
+        }
+      }
+#else
+      int c = qblock_next_hit(sg, ws.cb[qcb_lo(l)], c1);
 #pragma unroll 1
       while (__any(c < c1)) {
         if (c < c1) {
-          const float *p = sg + bw_con_off(c);
-          const float tau = p[0], dist = p[4];
-          const v3 pe = l == 0 ? b.x[0] : vfma(rv, tau, b.x[l]);
-          ocontact_vel_pe(g, SC, false, r - dist, pe, V(p[1], p[2], p[3]), 1e-6f + dist, im, b.x[l], b.v[l], b.w[l], dV[l],
-                          dW[l]);
+          apply(sg + bw_con_off(c));
           ++c;
         }
         c = qblock_next_hit(sg, c, c1);
       }
+#endif
     }
     return;
   }

@@ -28,7 +28,7 @@ rec = []
 try:
     for t in range(steps):
         buf[:] = 0
-        s = e.step(s, rng.uniform(-1, 1, (B, 8)).astype(np.float32), flags=orc.F_EPISODE | orc.F_AUTORESET, nthreads=8, inplace=True)
+        s = e.step(s, rng.uniform(-1, 1, (B, 8)).astype(np.float32), flags=orc.F_EPISODE | orc.F_AUTORESET, nthreads=1, inplace=True)  # (the hook keeps its cursor in globals: one thread)
         rec.append(buf.copy())
 finally:
     L.orc_items_record(None, 0); L.orc_flops_set_mode(orc.FLOPS_REF_PAIRS)
@@ -106,6 +106,7 @@ def wave_rounds(slots):  # (64, 3) item counts of a wave's lanes in a substep ->
     return rounds
 if Bn % 64 == 0:
     now_w, now_b, pool_w, pool_b, blk_items, wav_items = [], [], [], [], [], []
+    once_b, once_w, once_items = [], [], []  # the torso's items once per quad (POB_QUAD_TORSO_ONCE)
     for t in range(S):
         ls = lane_slots(rec[t]).reshape(Bn // 16, 64, NS, 3)  # (waves, lanes, NSUB, 3)
         wi = ls.sum((1, 3))  # (waves, NSUB) items per wave and substep
@@ -119,6 +120,16 @@ if Bn % 64 == 0:
         now_w.append(r_now.sum(1)); pool_w.append(r_pool.sum(1))
         now_b.append(r_now.sum(1).reshape(-1, 4).sum(1)); pool_b.append(R.sum(1))
         blk_items.append(bi); wav_items.append(wi)
+        # the torso's items published by leg lane 0 alone: the other three lanes hold their own only
+        lo = ls.copy().reshape(-1, 16, 4, NS, 3)
+        lo[:, :, 1:, :, 0] = 0
+        bo = lo.sum((1, 2, 4)).reshape(-1, 4, NS).sum(1)  # (blocks, NSUB)
+        Ro = -(-bo // 8)
+        r_once = np.zeros_like(r_now)
+        for w in range(4):
+            first = (w + np.arange(NS)) % 4
+            r_once[w::4] = np.maximum(0, -(-(Ro - first[None, :]) // 4))
+        once_b.append(Ro.sum(1)); once_w.append(r_once.sum(1)); once_items.append(bo)
     now_w, pool_w, now_b, pool_b = map(np.stack, (now_w, pool_w, now_b, pool_b))
     bi, wi = np.concatenate(blk_items).ravel(), np.concatenate(wav_items).ravel()
     print(f"four-lane: items per wave and collide substep mean {wi.mean():.1f} p90 {np.percentile(wi, 90):.0f} max {wi.max()}; "
@@ -130,3 +141,8 @@ if Bn % 64 == 0:
           f"max {now_w.max()}, slowest wave per step {now_w.max(1).mean():.2f}, per block {now_b.mean():.2f}")
     print(f"four-lane pooled walk:   rounds per wave per step mean {pool_w.mean():.2f}, slowest wave per step "
           f"{pool_w.max(1).mean():.2f}, per block {pool_b.mean():.2f} ({100 * (pool_b.mean() / now_b.mean() - 1):+.0f} %)")
+    once_b, once_w, bo = np.stack(once_b), np.stack(once_w), np.concatenate(once_items).ravel()
+    print(f"four-lane pooled walk, torso once per quad: items per env and collide substep {bi.sum() / (S * Bn * NS):.3f} -> "
+          f"{bo.sum() / (S * Bn * NS):.3f}, rounds per block per step {pool_b.mean():.2f} -> {once_b.mean():.2f}, slowest block per step "
+          f"{pool_b.max(1).mean():.2f} -> {once_b.max(1).mean():.2f}, slowest wave per step {pool_w.max(1).mean():.2f} -> "
+          f"{once_w.max(1).mean():.2f}, largest block load {bi.max()} -> {bo.max()}")
