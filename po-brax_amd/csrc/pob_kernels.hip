@@ -762,13 +762,23 @@ __device__ __forceinline__ void quad_store_dyn(const StatePtrs &in, const StateP
 }
 
 // Wall-contact overflow handling of the four-lane kernel (MODE): 0 = in the kernel (the position
-// and velocity passes re-walk an overflowing lane's faces); 1 = the fast launch: every wave
+// and velocity passes re-walk an overflowing lane's faces); 1 = the fast pass: every wave
 // records in ovf_mark[its first env] whether one of its lanes overflowed the contact store (its
 // first store clears the mark: AntGather's no-wall pass never reaches the overflow test), and a
-// wave that overflowed stores nothing else and exits; 2 = the fix-up launch right after it: only
-// the marked waves run, the whole step with the re-walks.  The re-walk code's mere presence in
-// the substep loop cost 15 % (HH) through register pressure (profiles/r6a_ab.txt); split, the
-// common launch carries none of it.  The marks are a caller-provided scratch array (pob_state
+// wave that overflowed stores nothing else; 2 / 3 = the fix-up: the marked waves run the whole
+// step again from the step's inputs, with the re-walks.  The re-walk code's mere presence in the
+// substep loop cost 15 % (HH) through register pressure (profiles/r6a_ab.txt); apart, the common
+// path carries none of it.  Where the fix-up runs:
+// * the block-cooperative kernels (COOP below: HH / TAG in 256-thread blocks, the headline
+//   workload) call it themselves after the substep loop (quad_fixup, out of line, MODE 3:
+//   nothing of the fast pass is live there) -- one launch per step.  Until round 10 it was a
+//   second launch of the whole grid, which found nothing on the bench workloads in every step
+//   and cost HH B = 65 536 0.1265 -> 0.1240 ms, TAG 0.0962 -> 0.0938 (profiles/r11a/ab.txt);
+// * the per-wave kernels (AntGather, the mixed launch, one-wave blocks) keep the second launch
+//   (MODE 2: k_step_quad<.., 2> / k_step_mixed<.., 2> test the marks): with the call in them
+//   their fast loops spill (GA B = 65 536 0.1142 -> 0.2138 ms, mixed fp16 B = 32 768 0.1144 ->
+//   0.1186; POB_QUAD_FUSE_WAVE=1 builds that form).
+// The marks are a caller-provided scratch array (pob_state
 // ovf_mark, ABI v8) outside every output -- round 5's in-band mark (a signalling NaN in the
 // wave's first obs element) could be forged by a first_obs row that AUTORESET copies -- and
 // every wave of the fast launch writes its mark, so the array needs no initialisation; slices
@@ -776,16 +786,35 @@ __device__ __forceinline__ void quad_store_dyn(const StatePtrs &in, const StateP
 // COOP (MODE 1, HH / TAG, 256-thread blocks: k_step_quad): the block's four waves pool the wall
 // walk (pob_quad.h qwalls_detect_block), with two block barriers per collide substep -- so no
 // wave of such a block leaves the substep loop early: a wave past the batch runs it as a replay
-// of env B - 1 with no items, an overflowed block runs it to the end, and both return after it.
+// of env B - 1 with no items and returns after it, an overflowed block runs it to the end and
+// its live waves then go to the fix-up (past the last block barrier: after it a wave reads and
+// writes its own LDS region only, and the fix-up holds no block barrier).
+// (tid: the thread's index in its block, passed in -- the fix-up reads no vector implicit
+// argument, so the kernel keeps none live across the fast loop for it.  It takes gt and the LDS
+// addresses of the wave's region, the block's regions and the leg table, and reads the kernel's
+// arguments from the kernel-argument segment itself, whose address the kernel hands it (the
+// intrinsic yields it in a kernel only: in a function it is lowered to null): passed in, the 52 state pointers were live
+// from the kernel's start to the call, and the fast loop spilled scalars around them -- 180
+// v_readlane in the HH kernel, which cost the whole gain of the dropped launch, HH B = 65 536
+// 0.1278 ms with and without it; profiles/r11a/ab.txt)
+#ifndef POB_QUAD_FUSE_WAVE
+#define POB_QUAD_FUSE_WAVE 0  // (1: the per-wave kernels call the fix-up too -- measured slower, above)
+#endif
+template <int KIND, typename QT>
+__device__ __attribute__((noinline)) void quad_fixup(const void *kargs, int gt, uint32_t stg_at, uint32_t lds_at,
+                                                     uint32_t legtab_at);
+typedef __attribute__((address_space(3))) float lds_float;
+POB_D uint32_t lds_addr(const float *p) { return (uint32_t)(size_t)(const lds_float *)p; }
+POB_D float *lds_ptr(const uint32_t at) { return (float *)(lds_float *)(size_t)at; }
 template <int KIND, typename QT, bool LEG = false, int MODE = 0, bool COOP = false>
 POB_D void step_quad_body(csys_t *Sp, const int B, const StatePtrs &in, const float *__restrict__ act,
-                          const StatePtrs &out, const uint32_t flags, const int L, const int gt, float *lds,
-                          const float *legtab) {
+                          const StatePtrs &out, const uint32_t flags, const int L, const int gt, const int tid,
+                          float *lds, const float *legtab) {
   csys_t &S = *Sp;
-  const int lane = (int)threadIdx.x & 63;
+  const int lane = tid & 63;
   POB_TS_DECL();  // timing experiment only (POB_EXP_TIMING)
   POB_TS(0);
-  float *stg = lds + ((int)threadIdx.x >> 6) * POB_STAGE_FLOATS;  // this wave's region
+  float *stg = lds + (tid >> 6) * POB_STAGE_FLOATS;  // this wave's region
   const QLds Ls{stg, lane};
   int b = gt >> 2;
   int k = gt & 3;
@@ -799,7 +828,7 @@ POB_D void step_quad_body(csys_t *Sp, const int B, const StatePtrs &in, const fl
   int b_first = (gt - lane) >> 2;
   const bool dead = b_first >= B;  // (wave-uniform: a block's waves past the batch)
   if (!COOP && dead) return;       // (no barrier follows)
-  if (MODE == 2 && out.ovf_mark[b_first] == 0) return;  // (not marked)
+  if (MODE == 2 && out.ovf_mark[b_first] == 0) return;  // (the fix-up launch: not marked)
   if (MODE == 1 && lane == 0 && !dead) out.ovf_mark[b_first] = 0;  // (every wave: the passes that finish leave it)
   // (COOP: a wave past the batch stays for the block's barriers -- every lane replays env B - 1
   // from the last live wave's rows, as the lanes past the batch in that wave do, and stores nothing)
@@ -812,6 +841,17 @@ POB_D void step_quad_body(csys_t *Sp, const int B, const StatePtrs &in, const fl
   size_t r3 = (size_t)bl * N * 3, r4 = (size_t)bl * N * 4;
   // the same indices from an opaque copy of the thread index (after the substep loop: the copies
   // above are then dead across it, instead of held -- in practice spilled -- through it)
+  // a marked wave's step, over again from its inputs: in this launch (FUSED), or left to the
+  // fix-up launch (POB_EXP_NO_FIXUP_LAUNCH, timing experiment only: neither -- valid where no
+  // wave is marked)
+  constexpr bool FUSED = MODE == 1 && (COOP || POB_QUAD_FUSE_WAVE);
+  auto fixup = [&]() {
+#ifndef POB_EXP_NO_FIXUP_LAUNCH
+    if constexpr (FUSED)
+      quad_fixup<KIND, QT>((const void *)__builtin_amdgcn_kernarg_segment_ptr(), gt, lds_addr(stg), lds_addr(lds),
+                           lds_addr(legtab));
+#endif
+  };
   auto rederive = [&]() {
     int g2 = gt;
     asm volatile("" : "+v"(g2));
@@ -991,12 +1031,12 @@ POB_D void step_quad_body(csys_t *Sp, const int B, const StatePtrs &in, const fl
 #define POB_QUAD_SLOW_OOL 1  // (with POB_QUAD_FAST_PASS: the slow pass's substep out of line)
 #endif
     if constexpr (MODE == 1 && WALLS && COOP) {
-      // the fast launch, block-cooperative: every wave of the block runs every substep (two block
+      // the fast pass, block-cooperative: every wave of the block runs every substep (two block
       // barriers in each collide substep, qwalls_detect_block) and only then leaves -- a wave past
-      // the batch with nothing stored, an overflowed block (block-uniform) to the fix-up launch
+      // the batch with nothing stored, an overflowed block's (block-uniform) live waves to the fix-up
       const int capf = (int)((flags & POB_F_INT_BWCAP_MASK) >> POB_F_INT_BWCAP_SHIFT);
       const int hitf = (int)((flags & POB_F_INT_HITW_MASK) >> POB_F_INT_HITW_SHIFT);
-      QBlock blk{lds + QPOOL_OFF, __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), 0,
+      QBlock blk{lds + QPOOL_OFF, __builtin_amdgcn_readfirstlane(tid >> 6), 0,
                  capf != 0 ? capf : QBW_CAP, hitf != 0 ? hitf : QBW_HIT_ITEMS, dead, false};
 #pragma nounroll
       for (int it = 0; it < 2 * iters; ++it) {
@@ -1010,14 +1050,15 @@ POB_D void step_quad_body(csys_t *Sp, const int B, const StatePtrs &in, const fl
         qpbd_substep<WALLS, false, false, true>(Sp, LT, WT, bd, a, Ls, (it & 1) != 0, fric, nullptr, nullptr, &blk);
       }
       if (dead) return;
-      if (blk.ovf || (flags & POB_F_INT_FORCE_FIXUP)) {
+      if (__builtin_expect(blk.ovf || (flags & POB_F_INT_FORCE_FIXUP), 0)) {
         if (lane == 0) out.ovf_mark[b_first] = 1;
+        fixup();
         return;
       }
       break;
     }
     if (MODE == 1 && WALLS) {
-      // the fast launch: the store only; a wave with an overflowing lane leaves the step to the
+      // the fast pass: the store only; a wave with an overflowing lane leaves the step to the
       // fix-up launch (nothing of its state is written: every output store follows the physics)
       bool ovf = false;
 #pragma nounroll
@@ -1032,8 +1073,9 @@ POB_D void step_quad_body(csys_t *Sp, const int B, const StatePtrs &in, const fl
         qpbd_substep<WALLS, false, false>(Sp, LT, WT, bd, a, Ls, (it & 1) != 0, fric, nullptr, &ovf);
         if (__any(ovf)) break;
       }
-      if (__any(ovf) || (flags & POB_F_INT_FORCE_FIXUP)) {
+      if (__builtin_expect(__any(ovf) || (flags & POB_F_INT_FORCE_FIXUP), 0)) {
         if (lane == 0) out.ovf_mark[b_first] = 1;
+        fixup();
         return;
       }
       break;
@@ -1287,14 +1329,15 @@ __global__ __launch_bounds__(256, POB_QUAD_MIN_WAVES) void k_step_quad(const voi
                                                                        const float *__restrict__ act,
                                                                        const StatePtrs out, const uint32_t flags,
                                                                        const int L) {
-  static_assert(!COOP || (MODE == 1 && (KIND == POB_HEAVENHELL || KIND == POB_TAG)), "the cooperative walk: fast launch, HH / TAG");
+  static_assert(MODE <= 2, "MODE 3 is quad_fixup's");
+  static_assert(!COOP || (MODE == 1 && (KIND == POB_HEAVENHELL || KIND == POB_TAG)), "the cooperative walk: fast pass, HH / TAG");
   __shared__ __attribute__((aligned(16))) float lds[QL_FLOATS * 256];
   __shared__ __attribute__((aligned(16))) float legtab[POB_TAB_FLOATS];
   if (MODE == 2 && !quad_block_marked(B, out.ovf_mark, (int)(blockIdx.x * blockDim.x)))
     return;
   stage_leg_table((csys_t *)(size_t)sysp, legtab);
   step_quad_body<KIND, QT, false, MODE, COOP>((csys_t *)(size_t)sysp, B, in, act, out, flags, L,
-                                        (int)(blockIdx.x * blockDim.x + threadIdx.x), lds, legtab);
+                                        (int)(blockIdx.x * blockDim.x + threadIdx.x), (int)threadIdx.x, lds, legtab);
 }
 
 // AntGather at most three waves per SIMD (B <= 3 x 16 x SIMDs): the same kernel with the
@@ -1309,7 +1352,7 @@ __global__ __launch_bounds__(256, 3) void k_step_quad_ga3(const void *sysp, cons
   __shared__ __attribute__((aligned(16))) float legtab[POB_TAB_FLOATS];
   stage_leg_table((csys_t *)(size_t)sysp, legtab);
   step_quad_body<POB_GATHER, QT>((csys_t *)(size_t)sysp, B, in, act, out, flags, L,
-                                 (int)(blockIdx.x * blockDim.x + threadIdx.x), lds, legtab);
+                                 (int)(blockIdx.x * blockDim.x + threadIdx.x), (int)threadIdx.x, lds, legtab);
 }
 
 // The same fused step with the legacy spring dynamics (pob_params.legacy_spring; pob_quad.h
@@ -1322,7 +1365,7 @@ __global__ __launch_bounds__(256) void k_step_legacy(const void *sysp, const int
   __shared__ __attribute__((aligned(16))) float legtab[POB_TAB_FLOATS];
   stage_leg_table((csys_t *)(size_t)sysp, legtab);
   step_quad_body<KIND, QT, true>((csys_t *)(size_t)sysp, B, in, act, out, flags, L,
-                                 (int)(blockIdx.x * blockDim.x + threadIdx.x), lds, legtab);
+                                 (int)(blockIdx.x * blockDim.x + threadIdx.x), (int)threadIdx.x, lds, legtab);
 }
 
 // Mixed launch: segment k owns blocks [blk0_k, blk0_{k+1}); the segment index is
@@ -1345,6 +1388,59 @@ POB_D const void *uniform_ptr(const void *p) {
   const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
   const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
   return (const void *)(size_t)(((uint64_t)hi << 32) | lo);
+}
+
+// The fix-up of a marked wave (MODE 3 body), called by the fast pass after its substep loop.  The
+// kernel's arguments come from the kernel-argument segment, where they lie in order at their
+// natural alignment -- the layout of these structs (k_step_quad: every instantiation has the
+// one signature; k_step_mixed: the segment again from the block's index, a scalar).  A wave
+// starts on a multiple of 64 of gt in every kernel, so gt's low bits are the lane.
+struct QuadKArgs {
+  const void *sysp;
+  int B;
+  StatePtrs in;
+  const float *act;
+  StatePtrs out;
+  uint32_t flags;
+  int L;
+};
+struct MixKArgs {
+  MixArgs A;
+  uint32_t flags;
+  int L;
+};
+template <int KIND, typename QT>
+__device__ __attribute__((noinline)) void quad_fixup(const void *kargs, int gt, uint32_t stg_at, uint32_t lds_at,
+                                                     uint32_t legtab_at) {
+  // (a function's arguments arrive in vector registers: the wave-uniform ones back into scalars)
+  const auto uni = [](const uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+  lds_at = uni(lds_at);
+  const int tid = (int)((uni(stg_at) - lds_at) / (uint32_t)(POB_STAGE_FLOATS * sizeof(float))) * 64 + (gt & 63);
+  StatePtrs in, out;
+  if constexpr (KIND == POB_MIXED) {
+    typedef __attribute__((address_space(4))) const MixKArgs kargs_t;
+    kargs_t *ka = (kargs_t *)(size_t)uniform_ptr(kargs);
+    const int bx = (int)blockIdx.x;
+    int seg = 0;
+#pragma unroll
+    for (int k = 1; k < POB_MIX_MAX; ++k)
+      if (k < ka->A.n && bx >= ka->A.s[k].blk0) seg = k;
+    seg = __builtin_amdgcn_readfirstlane(seg);
+#define POB_SEL(f) in.f = ka->A.s[seg].in.f; out.f = ka->A.s[seg].out.f;
+    POB_STATE_FIELDS(POB_SEL)
+#undef POB_SEL
+    step_quad_body<KIND, QT, false, 3>((csys_t *)(size_t)uniform_ptr(ka->A.s[seg].sysp), ka->A.s[seg].B, in,
+                                       ka->A.s[seg].act, out, ka->flags, ka->L, gt, tid, lds_ptr(lds_at),
+                                       lds_ptr(uni(legtab_at)));
+  } else {
+    typedef __attribute__((address_space(4))) const QuadKArgs kargs_t;
+    kargs_t *ka = (kargs_t *)(size_t)uniform_ptr(kargs);
+#define POB_SEL(f) in.f = ka->in.f; out.f = ka->out.f;
+    POB_STATE_FIELDS(POB_SEL)
+#undef POB_SEL
+    step_quad_body<KIND, QT, false, 3>((csys_t *)(size_t)ka->sysp, ka->B, in, ka->act, out, ka->flags, ka->L, gt, tid,
+                                       lds_ptr(lds_at), lds_ptr(uni(legtab_at)));
+  }
 }
 
 #ifndef POB_MIXED_MIN_WAVES
@@ -1382,7 +1478,7 @@ __global__ __launch_bounds__(256, POB_MIXED_MIN_WAVES) void k_step_mixed(const M
     return;
   stage_leg_table((csys_t *)(size_t)sysp, legtab);
   step_quad_body<POB_MIXED, QT, false, MODE>((csys_t *)(size_t)sysp, B, in, act, out, flags, L,
-                                (bx - blk0) * 256 + (int)threadIdx.x, lds, legtab);
+                                (bx - blk0) * 256 + (int)threadIdx.x, (int)threadIdx.x, lds, legtab);
 }
 
 // ------------------------------------------------------------------ step, lane octets
@@ -2951,11 +3047,20 @@ static void launch_step_oct(int kind, int n_cu, hipStream_t st, const void *sp, 
   if (acc) launch_step_oct_g<QT, true>(kind, st, sp, B, pi, act, po, flags, L);
   else launch_step_oct_g<QT, false>(kind, st, sp, B, pi, act, po, flags, L);
 }
-// The fast + fix-up launches per kind (bit 1 << kind, mixed 16): HH B = 65 536 0.1877 ->
+// The fast pass with the fix-up apart (MODE 1: called by the block-cooperative kernels, a second
+// launch after the per-wave ones) per kind (bit 1 << kind, mixed 16), against the one-pass MODE 0
+// kernel: HH B = 65 536 0.1877 ->
 // 0.1634 ms, TAG 0.1192 -> 0.1055, GA 0.1148 -> 0.1145, mixed fp16 B = 32 768 0.1281 -> 0.1316
 // (profiles/r6b_ab.txt, r6c_ab.txt); since round 6's LDS contact pool (no scratch in the fast
 // launch) the mixed launch too: fp16 B = 32 768 0.1231 -> 0.1149 ms (profiles/r7h).
-// POB_QUAD_SPLIT=0 / 1 forces the one-launch form / the split.
+// POB_QUAD_SPLIT=0 forces the one-pass kernel, any other value the fast pass with its fix-up.
+// (the fix-up launch after a per-wave fast launch; POB_EXP_NO_FIXUP_LAUNCH, timing experiment
+// only: no fix-up at all, launched or called -- valid where no wave is marked)
+#ifdef POB_EXP_NO_FIXUP_LAUNCH
+#define POB_FIXUP_LAUNCH 0
+#else
+#define POB_FIXUP_LAUNCH (!POB_QUAD_FUSE_WAVE)
+#endif
 #ifndef POB_QUAD_SPLIT_KINDS
 #define POB_QUAD_SPLIT_KINDS 23
 #endif
@@ -2999,19 +3104,21 @@ static void launch_step_quad(int kind, bool legacy, int n_cu, hipStream_t st, co
     hipLaunchKernelGGL((k_step_quad_ga3<QT>), g, b, 0, st, sp, B, pi, act, po, flags, L);
     return;
   }
-  // walls: the fast launch, then the fix-up launch of its overflowing waves (MODE 1 / 2 above;
-  // without the caller's mark array the one-launch form)
+  // walls: the fast pass, whose overflowing waves run the fix-up -- in the same launch (the
+  // block-cooperative kernels), or in the fix-up launch after it (MODE 1 / 2 / 3 above; without
+  // the caller's mark array the one-pass form)
   const bool split = quad_split_launch(kind) && po.ovf_mark != nullptr;
   flags |= split ? quad_force_fixup() : 0u;
-  // 256-thread blocks of HH / TAG: the fast launch's block-cooperative wall walk
+  // 256-thread blocks of HH / TAG: the fast pass's block-cooperative wall walk
   const bool coop = split && bs == 256 && (kind == POB_HEAVENHELL || kind == POB_TAG);
   flags |= coop ? quad_block_cap() | quad_hit_width() : 0u;
+  const bool second = split && !coop && POB_FIXUP_LAUNCH;  // the fix-up launch
   switch (kind) {
     case POB_HEAVENHELL:
       if (split) {
         if (coop) hipLaunchKernelGGL((k_step_quad<POB_HEAVENHELL, QT, 1, true>), g, b, 0, st, sp, B, pi, act, po, flags, L);
         else hipLaunchKernelGGL((k_step_quad<POB_HEAVENHELL, QT, 1>), g, b, 0, st, sp, B, pi, act, po, flags, L);
-        hipLaunchKernelGGL((k_step_quad<POB_HEAVENHELL, QT, 2>), g, b, 0, st, sp, B, pi, act, po, flags, L);
+        if (second) hipLaunchKernelGGL((k_step_quad<POB_HEAVENHELL, QT, 2>), g, b, 0, st, sp, B, pi, act, po, flags, L);
       } else {
         hipLaunchKernelGGL((k_step_quad<POB_HEAVENHELL, QT>), g, b, 0, st, sp, B, pi, act, po, flags, L);
       }
@@ -3019,7 +3126,7 @@ static void launch_step_quad(int kind, bool legacy, int n_cu, hipStream_t st, co
     case POB_GATHER:
       if (split) {
         hipLaunchKernelGGL((k_step_quad<POB_GATHER, QT, 1>), g, b, 0, st, sp, B, pi, act, po, flags, L);
-        hipLaunchKernelGGL((k_step_quad<POB_GATHER, QT, 2>), g, b, 0, st, sp, B, pi, act, po, flags, L);
+        if (second) hipLaunchKernelGGL((k_step_quad<POB_GATHER, QT, 2>), g, b, 0, st, sp, B, pi, act, po, flags, L);
       } else {
         hipLaunchKernelGGL((k_step_quad<POB_GATHER, QT>), g, b, 0, st, sp, B, pi, act, po, flags, L);
       }
@@ -3028,7 +3135,7 @@ static void launch_step_quad(int kind, bool legacy, int n_cu, hipStream_t st, co
       if (split) {
         if (coop) hipLaunchKernelGGL((k_step_quad<POB_TAG, QT, 1, true>), g, b, 0, st, sp, B, pi, act, po, flags, L);
         else hipLaunchKernelGGL((k_step_quad<POB_TAG, QT, 1>), g, b, 0, st, sp, B, pi, act, po, flags, L);
-        hipLaunchKernelGGL((k_step_quad<POB_TAG, QT, 2>), g, b, 0, st, sp, B, pi, act, po, flags, L);
+        if (second) hipLaunchKernelGGL((k_step_quad<POB_TAG, QT, 2>), g, b, 0, st, sp, B, pi, act, po, flags, L);
       } else {
         hipLaunchKernelGGL((k_step_quad<POB_TAG, QT>), g, b, 0, st, sp, B, pi, act, po, flags, L);
       }
@@ -3238,10 +3345,10 @@ int pob_step_mixed(int n, pob_env *const *envs, const int *B, const pob_state *i
     flags |= quad_force_fixup();
     if (envs[0]->sys.qp_f16) {
       hipLaunchKernelGGL((k_step_mixed<__half, 1>), g, dim3(256), 0, st, A, flags, episode_length);
-      hipLaunchKernelGGL((k_step_mixed<__half, 2>), g, dim3(256), 0, st, A, flags, episode_length);
+      if (POB_FIXUP_LAUNCH) hipLaunchKernelGGL((k_step_mixed<__half, 2>), g, dim3(256), 0, st, A, flags, episode_length);
     } else {
       hipLaunchKernelGGL((k_step_mixed<float, 1>), g, dim3(256), 0, st, A, flags, episode_length);
-      hipLaunchKernelGGL((k_step_mixed<float, 2>), g, dim3(256), 0, st, A, flags, episode_length);
+      if (POB_FIXUP_LAUNCH) hipLaunchKernelGGL((k_step_mixed<float, 2>), g, dim3(256), 0, st, A, flags, episode_length);
     }
   } else if (envs[0]->sys.qp_f16) {
     hipLaunchKernelGGL((k_step_mixed<__half>), g, dim3(256), 0, st, A, flags, episode_length);
