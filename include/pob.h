@@ -261,6 +261,42 @@ int pob_gru_policy_act(const pob_gru *g, int B, int total, int first, const floa
                        uint32_t *key_io, int deterministic, const float *reset, float *h_io, float *action,
                        float *logp, float *raw, float *logits, float *obs_copy, float *h_in_copy, void *stream);
 
+/* ---- running observation normaliser (additive to ABI v8): brax PPO's normalize_observations
+ * (brax <= 0.0.12 training/normalization.py [ext]); results equal obsnorm_accumulate_ref /
+ * obsnorm_update_ref / pob_obsnorm_apply of csrc/pob_mlp.h bit for bit (DESIGN.md "Observation
+ * normaliser": formulas, summation order).  State, all caller-owned device memory: count
+ * (float64, 1 element, initially 0) and table (float32, (3, D): row 0 mean, initially 0; row 1
+ * scale, initially 1; row 2 m2, the running variance sum, initially 1).  1 <= D <= 256.
+ *
+ * pob_obsnorm_accumulate: sums (2, D) float64 = per column sum d and sum d^2, d = obs[n][f] -
+ * mean[f] in float64, over the N rows of a row-major (N, D) array, in a fixed order (chunks of
+ * 1024 rows, rows ascending, then chunks ascending) that depends on N and D only.  workspace:
+ * pob_obsnorm_workspace_bytes(N, D) bytes, the chunk partials; the library never allocates.
+ * pob_obsnorm_update: sums is (R, 2, D), one pair per shard in rank order, n_new the row count
+ * over all shards; count and table are finished in place by one block that reads nothing on
+ * the host (capturable). */
+int pob_obsnorm_workspace_bytes(long long N, int D, long long *bytes);
+int pob_obsnorm_accumulate(const float *obs, long long N, int D, const float *table, double *workspace,
+                           double *sums /* (2, D) */, void *stream);
+int pob_obsnorm_update(double *count_io, float *table_io, int D, const double *sums, int R, long long n_new,
+                       void *stream);
+/* The forward entry points with the normaliser fused into the observation tile load: the
+ * network sees clip((x - mean[f]) * scale[f], +-norm_clip) (two float32 roundings; norm_clip <= 0:
+ * no clamp; a NaN stays NaN), obs_copy still receives the raw rows, the hidden state is never
+ * normalised.  norm: the (3, D) table, rows 0 and 1 are read at launch time; NULL = no
+ * normalisation, the results of the entry point without the suffix. */
+int pob_mlp_forward_norm(const pob_mlp *mlp, int B, const float *x, const float *theta, float *y, const float *norm,
+                         float norm_clip, void *stream);
+int pob_policy_act_norm(const pob_mlp *mlp, int B, int total, int first, const float *obs, const float *theta,
+                        uint32_t *key_io, int deterministic, float *action, float *logp, float *raw, float *logits,
+                        float *obs_copy, const float *norm, float norm_clip, void *stream);
+int pob_gru_forward_norm(const pob_gru *g, int B, const float *x, const float *theta, const float *reset, float *h_io,
+                         float *y, float *h_in_copy, const float *norm, float norm_clip, void *stream);
+int pob_gru_policy_act_norm(const pob_gru *g, int B, int total, int first, const float *obs, const float *theta,
+                            uint32_t *key_io, int deterministic, const float *reset, float *h_io, float *action,
+                            float *logp, float *raw, float *logits, float *obs_copy, float *h_in_copy, const float *norm,
+                            float norm_clip, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

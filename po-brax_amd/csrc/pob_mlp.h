@@ -183,7 +183,78 @@ POB_MLP_D void pob_tanh_normal(const float loc, const float s, float u, float &a
   term = t1 - ld;
 }
 
+// ---------------------------------------------------------------------------- observation normaliser
+// The running normaliser of brax <= 0.0.12 training/normalization.py [ext] (DESIGN.md "Observation
+// normaliser").  State: count (float64), table (3, D) float32 = mean, scale, m2.  What an actor
+// kernel does to a staged observation element of column f: one float32 subtract, one float32
+// multiply (no contraction), then the clamp; clip <= 0 turns the clamp off.  A NaN stays NaN.
+#define POB_OBSNORM_CHUNK 1024  // rows of one chunk of the statistics' summation order
+POB_MLP_D float pob_obsnorm_apply(const float x, const float mean, const float scale, const float clip) {
+  float t = (x - mean) * scale;
+  if (clip > 0.0f) { t = t < -clip ? -clip : t; t = t > clip ? clip : t; }
+  return t;
+}
+// One row into a chunk's accumulator pair of a column: d is centred on the OLD mean.
+POB_MLP_D void pob_obsnorm_step(const float x, const float mean, double &S1, double &S2) {
+  const double d = (double)x - (double)mean;
+  S1 = S1 + d;
+  S2 = __builtin_fma(d, d, S2);
+}
+// The update of one column from its sums S1 = sum d, S2 = sum d^2 over n_new new rows (Welford in
+// one pass: m2 grows by sum (x - mean')(x - mean) = S2 - S1^2 / total).  Returns the new count.
+POB_MLP_D double pob_obsnorm_finish(const double count, const double n_new, const double S1, const double S2, float &mean,
+                                    float &scale, float &m2) {
+  const double total = count + n_new;
+  const double t = S1 / total;
+  mean = (float)((double)mean + t);
+  m2 = (float)((double)m2 + __builtin_fma(-S1, t, S2));
+  double v = (double)m2 / (total + 1.0);
+  v = v < 1e-6 ? 1e-6 : v;
+  v = v > 1e6 ? 1e6 : v;
+  scale = mlp_rcp(mlp_sqrt((float)v));
+  return total;
+}
+
 #ifdef POB_MLP_HOST
+// sums (2, D) float64 of x (N, D) against table row 0 (mean): rows cut into chunks of
+// POB_OBSNORM_CHUNK, a chunk's pair per column from +0.0 in ascending row order, the chunk
+// partials added per column in ascending chunk order from +0.0.  The order depends on N and D only.
+static inline void obsnorm_accumulate_ref(const float *x, const long long N, const int D, const float *table, double *sums) {
+  for (int f = 0; f < D; ++f) {
+    double T1 = 0.0, T2 = 0.0;
+    for (long long r0 = 0; r0 < N; r0 += POB_OBSNORM_CHUNK) {
+      const long long r1 = r0 + POB_OBSNORM_CHUNK < N ? r0 + POB_OBSNORM_CHUNK : N;
+      double S1 = 0.0, S2 = 0.0;
+      for (long long r = r0; r < r1; ++r) pob_obsnorm_step(x[r * D + f], table[f], S1, S2);
+      T1 = T1 + S1;
+      T2 = T2 + S2;
+    }
+    sums[f] = T1;
+    sums[D + f] = T2;
+  }
+}
+// count, table (3, D) updated in place from sums (R, 2, D), one pair per shard in rank order
+// (added per column in ascending r from +0.0), n_new = the row count over all shards.
+static inline void obsnorm_update_ref(double *count, float *table, const int D, const double *sums, const int R,
+                                      const long long n_new) {
+  double total = *count;
+  for (int f = 0; f < D; ++f) {
+    double S1 = 0.0, S2 = 0.0;
+    for (int r = 0; r < R; ++r) {
+      S1 = S1 + sums[((long long)r * 2) * D + f];
+      S2 = S2 + sums[((long long)r * 2 + 1) * D + f];
+    }
+    total = pob_obsnorm_finish(*count, (double)n_new, S1, S2, table[f], table[D + f], table[2 * D + f]);
+  }
+  *count = total;
+}
+// x (B, D) normalised in place by table rows 0, 1 (NULL: left as it is)
+static inline void obsnorm_apply_ref(float *x, const long long B, const int D, const float *table, const float clip) {
+  if (!table) return;
+  for (long long b = 0; b < B; ++b)
+    for (int f = 0; f < D; ++f) x[b * D + f] = pob_obsnorm_apply(x[b * D + f], table[f], table[D + f], clip);
+}
+
 // ---------------------------------------------------------------------------- restatement
 // theta packing: W_0 (in_0, out_0) row-major, b_0 (out_0), W_1, b_1, ..  (sizes[0] = input)
 static inline long long mlp_param_count(const int n_layers, const int *sizes) {

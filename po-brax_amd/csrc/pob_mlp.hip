@@ -109,15 +109,18 @@ POB_MLP_D void mlp_tile_store(float *dst, const float *img, const int f0, const 
 
 // features [0, D) of an image <- rows [b0, b0 + 32) of a row-major (B, D) array x: coalesced
 // loads, MLP_STAGE in flight per lane, tail rows repeating the last valid one.  copy (may be
-// NULL) receives the valid rows as staged.  reset (may be NULL): a row whose reset[b] != 0 is
-// staged as +0 in every feature.
+// NULL) receives the valid rows as loaded.  reset (may be NULL): a row whose reset[b] != 0 is
+// staged as +0 in every feature.  NORM: the image takes pob_obsnorm_apply of the value, with the
+// column's mean and scale (rows 0 and 1 of the (3, D) table `norm`) loaded along with it; copy
+// keeps the raw row.
+template <bool NORM>
 POB_MLP_D void mlp_tile_load(float *img, const float *x, const int D, const int b0, const int valid, float *copy,
-                             const float *reset, const int lane) {
+                             const float *reset, const float *norm, const float clip, const int lane) {
   // element e = row D + col of the tile's 32 contiguous rows; a lane's elements are 64 apart
   const int dq = 64 / D, dr = 64 - dq * D;
   int row = lane / D, col = lane - row * D;
   for (int e0 = lane; e0 < MLP_ROWS * D; e0 += 64 * MLP_STAGE) {
-    float v[MLP_STAGE];
+    float v[MLP_STAGE], mu[NORM ? MLP_STAGE : 1], sc[NORM ? MLP_STAGE : 1];
     int at[MLP_STAGE];  // the element's place in the image (-1: past the tile), bit 30: a row to copy out
 #pragma unroll
     for (int u = 0; u < MLP_STAGE; ++u) {
@@ -125,6 +128,10 @@ POB_MLP_D void mlp_tile_load(float *img, const float *x, const int D, const int 
       const int rr = row < valid ? row : valid - 1;  // tail rows repeat the last one
       v[u] = in_tile ? x[(size_t)(b0 + rr) * D + col] : 0.0f;
       if (reset) v[u] = (in_tile && reset[b0 + rr] != 0.0f) ? 0.0f : v[u];
+      if (NORM) {
+        mu[u] = in_tile ? norm[col] : 0.0f;
+        sc[u] = in_tile ? norm[D + col] : 0.0f;
+      }
       at[u] = in_tile ? (col * MLP_PITCH + row) | (row < valid ? 1 << 30 : 0) : -1;
       row += dq; col += dr;
       if (col >= D) { col -= D; ++row; }
@@ -132,18 +139,20 @@ POB_MLP_D void mlp_tile_load(float *img, const float *x, const int D, const int 
 #pragma unroll
     for (int u = 0; u < MLP_STAGE; ++u) {
       if (at[u] >= 0) {
-        img[at[u] & 0xFFFFF] = v[u];
         if (copy && (at[u] >> 30)) copy[(size_t)b0 * D + e0 + 64 * u] = v[u];
+        img[at[u] & 0xFFFFF] = NORM ? pob_obsnorm_apply(v[u], mu[u], sc[u], clip) : v[u];
       }
     }
   }
 }
 
 // The forward of one tile.  Returns the image holding the last layer's output.
+template <bool NORM>
 POB_MLP_D float *mlp_tile_forward(const MlpDesc &d, float *imgA, float *imgB, const int B, const int b0, const float *x,
-                                  const float *theta, float *obs_copy, const int lane) {
+                                  const float *theta, float *obs_copy, const float *norm, const float clip,
+                                  const int lane) {
   const int valid = B - b0 < MLP_ROWS ? B - b0 : MLP_ROWS;
-  mlp_tile_load(imgA, x, d.sizes[0], b0, valid, obs_copy, nullptr, lane);
+  mlp_tile_load<NORM>(imgA, x, d.sizes[0], b0, valid, obs_copy, nullptr, norm, clip, lane);
   __syncthreads();
   float *src = imgA, *dst = imgB;
   const float *W = theta;
@@ -158,13 +167,13 @@ POB_MLP_D float *mlp_tile_forward(const MlpDesc &d, float *imgA, float *imgB, co
   return src;
 }
 
-template <int H>
+template <int H, bool NORM>
 __global__ __launch_bounds__(64) void k_mlp_forward(const MlpDesc d, const int split, const int B, const float *x,
-                                                    const float *theta, float *y) {
+                                                    const float *theta, float *y, const float *norm, const float clip) {
   __shared__ float img[H * MLP_PITCH];
   float *imgA = img, *imgB = img + split * MLP_PITCH;
   const int lane = threadIdx.x, b0 = blockIdx.x * MLP_ROWS;
-  const float *out = mlp_tile_forward(d, imgA, imgB, B, b0, x, theta, nullptr, lane);
+  const float *out = mlp_tile_forward<NORM>(d, imgA, imgB, B, b0, x, theta, nullptr, norm, clip, lane);
   const int valid = B - b0 < MLP_ROWS ? B - b0 : MLP_ROWS;
   mlp_tile_store(y, out, 0, d.sizes[d.n_layers], b0, valid, lane);
 }
@@ -211,15 +220,16 @@ POB_MLP_D void policy_tile_head(float *L, float *T, const int A, const int b0, c
   }
 }
 
-template <int H>
+template <int H, bool NORM>
 __global__ __launch_bounds__(64) void k_policy_act(const MlpDesc d, const int split, const int B, const int total,
                                                    const int first, const float *obs, const float *theta,
                                                    const uint32_t *key, const int deterministic, float *action,
-                                                   float *logp, float *raw, float *logits, float *obs_copy) {
+                                                   float *logp, float *raw, float *logits, float *obs_copy,
+                                                   const float *norm, const float clip) {
   __shared__ float img[H * MLP_PITCH];
   float *imgA = img, *imgB = img + split * MLP_PITCH;
   const int lane = threadIdx.x, b0 = blockIdx.x * MLP_ROWS;
-  float *L = mlp_tile_forward(d, imgA, imgB, B, b0, obs, theta, obs_copy, lane);
+  float *L = mlp_tile_forward<NORM>(d, imgA, imgB, B, b0, obs, theta, obs_copy, norm, clip, lane);
   float *T = L == imgA ? imgB : imgA;  // the per-component log-probability terms
   const int valid = B - b0 < MLP_ROWS ? B - b0 : MLP_ROWS;
   const int A = d.sizes[d.n_layers] >> 1;
@@ -280,16 +290,17 @@ POB_MLP_D void gru_cell(const float *C, float *N, const float *g, const int I, c
 
 // The forward of one tile; h' is stored to h_io on the way.  Returns the image holding the post-
 // MLP's output; `other` is the ping-pong image it is not in.
+template <bool NORM>
 POB_MLP_D float *gru_tile_forward(const GruDesc &d, float *pool, const int B, const int b0, const float *x,
                                   const float *theta, const float *reset, float *h_io, float *obs_copy, float *h_in_copy,
-                                  float *&other, const int lane) {
+                                  float *&other, const float *norm, const float clip, const int lane) {
   const int valid = B - b0 < MLP_ROWS ? B - b0 : MLP_ROWS;
   const int I = d.pre[d.n_pre], H = d.hid;
   float *C = pool, *N = C + (I + H) * MLP_PITCH;
   float *P0 = N + H * MLP_PITCH, *P1 = P0 + d.p_rows[0] * MLP_PITCH;
   int pp = 0;
-  mlp_tile_load(d.n_pre ? P0 : C, x, d.pre[0], b0, valid, obs_copy, nullptr, lane);
-  mlp_tile_load(C + I * MLP_PITCH, h_io, H, b0, valid, h_in_copy, reset, lane);
+  mlp_tile_load<NORM>(d.n_pre ? P0 : C, x, d.pre[0], b0, valid, obs_copy, nullptr, norm, clip, lane);
+  mlp_tile_load<false>(C + I * MLP_PITCH, h_io, H, b0, valid, h_in_copy, reset, nullptr, 0.0f, lane);  // h: never normalised
   __syncthreads();
   const float *W = theta;
   float *src = P0;
@@ -325,27 +336,29 @@ POB_MLP_D float *gru_tile_forward(const GruDesc &d, float *pool, const int B, co
   return src;
 }
 
-template <int R>
+template <int R, bool NORM>
 __global__ __launch_bounds__(64) void k_gru_forward(const GruDesc d, const int B, const float *x, const float *theta,
-                                                    const float *reset, float *h_io, float *y, float *h_in_copy) {
+                                                    const float *reset, float *h_io, float *y, float *h_in_copy,
+                                                    const float *norm, const float clip) {
   __shared__ float pool[R * MLP_PITCH];
   const int lane = threadIdx.x, b0 = blockIdx.x * MLP_ROWS;
   float *other;
-  const float *out = gru_tile_forward(d, pool, B, b0, x, theta, reset, h_io, nullptr, h_in_copy, other, lane);
+  const float *out = gru_tile_forward<NORM>(d, pool, B, b0, x, theta, reset, h_io, nullptr, h_in_copy, other, norm, clip, lane);
   const int valid = B - b0 < MLP_ROWS ? B - b0 : MLP_ROWS;
   mlp_tile_store(y, out, 0, d.post[d.n_post - 1], b0, valid, lane);
 }
 
-template <int R>
+template <int R, bool NORM>
 __global__ __launch_bounds__(64) void k_gru_policy_act(const GruDesc d, const int B, const int total, const int first,
                                                        const float *obs, const float *theta, const uint32_t *key,
                                                        const int deterministic, const float *reset, float *h_io,
                                                        float *action, float *logp, float *raw, float *logits,
-                                                       float *obs_copy, float *h_in_copy) {
+                                                       float *obs_copy, float *h_in_copy, const float *norm,
+                                                       const float clip) {
   __shared__ float pool[R * MLP_PITCH];
   const int lane = threadIdx.x, b0 = blockIdx.x * MLP_ROWS;
   float *T;  // the per-component log-probability terms
-  float *L = gru_tile_forward(d, pool, B, b0, obs, theta, reset, h_io, obs_copy, h_in_copy, T, lane);
+  float *L = gru_tile_forward<NORM>(d, pool, B, b0, obs, theta, reset, h_io, obs_copy, h_in_copy, T, norm, clip, lane);
   const int valid = B - b0 < MLP_ROWS ? B - b0 : MLP_ROWS;
   const int A = d.post[d.n_post - 1] >> 1;
   policy_tile_head(L, T, A, b0, valid, total, first, key, deterministic, action, logp, raw, logits, lane);
@@ -373,13 +386,17 @@ static int image_rows(const MlpDesc &d, bool head, int &split) {
   return rows <= 64 ? 0 : (rows <= 152 ? 1 : (rows <= 288 ? 2 : 3));
 }
 
-#define MLP_DISPATCH(KERNEL, cls, ...)                                                      \
-  switch (cls) {                                                                            \
-    case 0: hipLaunchKernelGGL((KERNEL<64>), grid, dim3(64), 0, st, __VA_ARGS__); break;    \
-    case 1: hipLaunchKernelGGL((KERNEL<152>), grid, dim3(64), 0, st, __VA_ARGS__); break;   \
-    case 2: hipLaunchKernelGGL((KERNEL<288>), grid, dim3(64), 0, st, __VA_ARGS__); break;   \
-    default: hipLaunchKernelGGL((KERNEL<512>), grid, dim3(64), 0, st, __VA_ARGS__); break;  \
+// the normalising instantiation only where a table is given: the plain one is the code it was
+#define MLP_DISPATCH_N(KERNEL, N, cls, ...)                                                    \
+  switch (cls) {                                                                               \
+    case 0: hipLaunchKernelGGL((KERNEL<64, N>), grid, dim3(64), 0, st, __VA_ARGS__); break;    \
+    case 1: hipLaunchKernelGGL((KERNEL<152, N>), grid, dim3(64), 0, st, __VA_ARGS__); break;   \
+    case 2: hipLaunchKernelGGL((KERNEL<288, N>), grid, dim3(64), 0, st, __VA_ARGS__); break;   \
+    default: hipLaunchKernelGGL((KERNEL<512, N>), grid, dim3(64), 0, st, __VA_ARGS__); break;  \
   }
+#define MLP_DISPATCH(KERNEL, cls, ...)                                \
+  if (norm) { MLP_DISPATCH_N(KERNEL, true, cls, __VA_ARGS__, norm, norm_clip) } \
+  else { MLP_DISPATCH_N(KERNEL, false, cls, __VA_ARGS__, norm, norm_clip) }
 
 static int mlp_hip_check(hipError_t e, const char *what) {
   if (e == hipSuccess) return POB_OK;
@@ -419,7 +436,8 @@ int pob_mlp_param_count(const pob_mlp *m, long long *n) {
   return POB_OK;
 }
 
-int pob_mlp_forward(const pob_mlp *m, int B, const float *x, const float *theta, float *y, void *stream) {
+int pob_mlp_forward_norm(const pob_mlp *m, int B, const float *x, const float *theta, float *y, const float *norm,
+                         float norm_clip, void *stream) {
   if (!m) return pob_fail_msg(POB_EINVAL, "mlp is NULL");
   if (B < 1) return pob_fail_msg(POB_EINVAL, "mlp: batch size must be positive");
   if (!x || !theta || !y) return pob_fail_msg(POB_EINVAL, "mlp: NULL argument");
@@ -431,9 +449,13 @@ int pob_mlp_forward(const pob_mlp *m, int B, const float *x, const float *theta,
   return mlp_hip_check(hipGetLastError(), "k_mlp_forward launch");
 }
 
-int pob_policy_act(const pob_mlp *m, int B, int total, int first, const float *obs, const float *theta,
-                   uint32_t *key_io, int deterministic, float *action, float *logp, float *raw, float *logits,
-                   float *obs_copy, void *stream) {
+int pob_mlp_forward(const pob_mlp *m, int B, const float *x, const float *theta, float *y, void *stream) {
+  return pob_mlp_forward_norm(m, B, x, theta, y, nullptr, 0.0f, stream);
+}
+
+int pob_policy_act_norm(const pob_mlp *m, int B, int total, int first, const float *obs, const float *theta,
+                        uint32_t *key_io, int deterministic, float *action, float *logp, float *raw, float *logits,
+                        float *obs_copy, const float *norm, float norm_clip, void *stream) {
   if (!m) return pob_fail_msg(POB_EINVAL, "mlp is NULL");
   const int out = m->d.sizes[m->d.n_layers];
   if (out & 1) return pob_fail_msg(POB_EINVAL, "policy: the last width must be even (loc and scale halves)");
@@ -451,6 +473,13 @@ int pob_policy_act(const pob_mlp *m, int B, int total, int first, const float *o
                obs_copy)
   if (!deterministic) hipLaunchKernelGGL(k_mlp_advance_key, dim3(1), dim3(1), 0, st, key_io);
   return mlp_hip_check(hipGetLastError(), "k_policy_act launch");
+}
+
+int pob_policy_act(const pob_mlp *m, int B, int total, int first, const float *obs, const float *theta,
+                   uint32_t *key_io, int deterministic, float *action, float *logp, float *raw, float *logits,
+                   float *obs_copy, void *stream) {
+  return pob_policy_act_norm(m, B, total, first, obs, theta, key_io, deterministic, action, logp, raw, logits, obs_copy,
+                             nullptr, 0.0f, stream);
 }
 
 }  // extern "C"
@@ -482,14 +511,17 @@ static int gru_plan(const GruDesc &d, bool head, int *p_rows) {
   return rows <= 96 ? 0 : (rows <= 192 ? 1 : (rows <= 288 ? 2 : (rows <= 512 ? 3 : 4)));
 }
 
-#define GRU_DISPATCH(KERNEL, cls, ...)                                                      \
-  switch (cls) {                                                                            \
-    case 0: hipLaunchKernelGGL((KERNEL<96>), grid, dim3(64), 0, st, __VA_ARGS__); break;    \
-    case 1: hipLaunchKernelGGL((KERNEL<192>), grid, dim3(64), 0, st, __VA_ARGS__); break;   \
-    case 2: hipLaunchKernelGGL((KERNEL<288>), grid, dim3(64), 0, st, __VA_ARGS__); break;   \
-    case 3: hipLaunchKernelGGL((KERNEL<512>), grid, dim3(64), 0, st, __VA_ARGS__); break;   \
-    default: hipLaunchKernelGGL((KERNEL<896>), grid, dim3(64), 0, st, __VA_ARGS__); break;  \
+#define GRU_DISPATCH_N(KERNEL, N, cls, ...)                                                    \
+  switch (cls) {                                                                               \
+    case 0: hipLaunchKernelGGL((KERNEL<96, N>), grid, dim3(64), 0, st, __VA_ARGS__); break;    \
+    case 1: hipLaunchKernelGGL((KERNEL<192, N>), grid, dim3(64), 0, st, __VA_ARGS__); break;   \
+    case 2: hipLaunchKernelGGL((KERNEL<288, N>), grid, dim3(64), 0, st, __VA_ARGS__); break;   \
+    case 3: hipLaunchKernelGGL((KERNEL<512, N>), grid, dim3(64), 0, st, __VA_ARGS__); break;   \
+    default: hipLaunchKernelGGL((KERNEL<896, N>), grid, dim3(64), 0, st, __VA_ARGS__); break;  \
   }
+#define GRU_DISPATCH(KERNEL, cls, ...)                                \
+  if (norm) { GRU_DISPATCH_N(KERNEL, true, cls, __VA_ARGS__, norm, norm_clip) } \
+  else { GRU_DISPATCH_N(KERNEL, false, cls, __VA_ARGS__, norm, norm_clip) }
 
 extern "C" {
 
@@ -538,8 +570,8 @@ int pob_gru_param_count(const pob_gru *g, long long *n) {
   return POB_OK;
 }
 
-int pob_gru_forward(const pob_gru *g, int B, const float *x, const float *theta, const float *reset, float *h_io,
-                    float *y, float *h_in_copy, void *stream) {
+int pob_gru_forward_norm(const pob_gru *g, int B, const float *x, const float *theta, const float *reset, float *h_io,
+                         float *y, float *h_in_copy, const float *norm, float norm_clip, void *stream) {
   if (!g) return pob_fail_msg(POB_EINVAL, "gru is NULL");
   if (B < 1) return pob_fail_msg(POB_EINVAL, "gru: batch size must be positive");
   if (!x || !theta || !y) return pob_fail_msg(POB_EINVAL, "gru: NULL argument");
@@ -552,9 +584,15 @@ int pob_gru_forward(const pob_gru *g, int B, const float *x, const float *theta,
   return mlp_hip_check(hipGetLastError(), "k_gru_forward launch");
 }
 
-int pob_gru_policy_act(const pob_gru *g, int B, int total, int first, const float *obs, const float *theta,
-                       uint32_t *key_io, int deterministic, const float *reset, float *h_io, float *action, float *logp,
-                       float *raw, float *logits, float *obs_copy, float *h_in_copy, void *stream) {
+int pob_gru_forward(const pob_gru *g, int B, const float *x, const float *theta, const float *reset, float *h_io,
+                    float *y, float *h_in_copy, void *stream) {
+  return pob_gru_forward_norm(g, B, x, theta, reset, h_io, y, h_in_copy, nullptr, 0.0f, stream);
+}
+
+int pob_gru_policy_act_norm(const pob_gru *g, int B, int total, int first, const float *obs, const float *theta,
+                            uint32_t *key_io, int deterministic, const float *reset, float *h_io, float *action,
+                            float *logp, float *raw, float *logits, float *obs_copy, float *h_in_copy, const float *norm,
+                            float norm_clip, void *stream) {
   if (!g) return pob_fail_msg(POB_EINVAL, "gru is NULL");
   const int out = g->d.post[g->d.n_post - 1];
   if (out & 1) return pob_fail_msg(POB_EINVAL, "policy: the last width must be even (loc and scale halves)");
@@ -573,6 +611,131 @@ int pob_gru_policy_act(const pob_gru *g, int B, int total, int first, const floa
                logp, raw, logits, obs_copy, h_in_copy)
   if (!deterministic) hipLaunchKernelGGL(k_mlp_advance_key, dim3(1), dim3(1), 0, st, key_io);
   return mlp_hip_check(hipGetLastError(), "k_gru_policy_act launch");
+}
+
+int pob_gru_policy_act(const pob_gru *g, int B, int total, int first, const float *obs, const float *theta,
+                       uint32_t *key_io, int deterministic, const float *reset, float *h_io, float *action, float *logp,
+                       float *raw, float *logits, float *obs_copy, float *h_in_copy, void *stream) {
+  return pob_gru_policy_act_norm(g, B, total, first, obs, theta, key_io, deterministic, reset, h_io, action, logp, raw,
+                                 logits, obs_copy, h_in_copy, nullptr, 0.0f, stream);
+}
+
+}  // extern "C"
+
+// ============================================================================ observation normaliser
+// The statistics of pob_mlp.h obsnorm_accumulate_ref / obsnorm_update_ref (the specification; DESIGN.md
+// "Observation normaliser").  k_obsnorm_accumulate: one lane per (chunk, column), consecutive lanes
+// on consecutive columns of a row (coalesced), the chunk's rows in ascending order into a float64
+// pair in registers, OBSNORM_STAGE loads in flight per lane; the pair goes to the workspace
+// (n_chunks, 2, D).  k_obsnorm_reduce: one lane per entry of (2, D) adds the chunk partials in
+// ascending chunk order.  k_obsnorm_update: one block finishes the table in place.  No atomics:
+// the order depends on N and D only.
+#define OBSNORM_STAGE 16
+#define OBSNORM_RSTAGE 32
+
+__global__ __launch_bounds__(256) void k_obsnorm_accumulate(const float *x, const long long N, const int D,
+                                                            const float *table, double *ws, const long long n_items) {
+  const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (g >= n_items) return;
+  const long long c = g / D;
+  const int f = (int)(g - c * D);
+  const long long r0 = c * POB_OBSNORM_CHUNK;
+  const int rows = N - r0 < POB_OBSNORM_CHUNK ? (int)(N - r0) : POB_OBSNORM_CHUNK;
+  const float mean = table[f];
+  const float *p = x + (size_t)r0 * D + f;
+  double S1 = 0.0, S2 = 0.0;
+  int r = 0;
+  for (; r + OBSNORM_STAGE <= rows; r += OBSNORM_STAGE) {
+    float v[OBSNORM_STAGE];
+#pragma unroll
+    for (int u = 0; u < OBSNORM_STAGE; ++u) v[u] = p[(size_t)(r + u) * D];
+#pragma unroll
+    for (int u = 0; u < OBSNORM_STAGE; ++u) pob_obsnorm_step(v[u], mean, S1, S2);
+  }
+  for (; r < rows; ++r) pob_obsnorm_step(p[(size_t)r * D], mean, S1, S2);
+  ws[(size_t)(2 * c) * D + f] = S1;
+  ws[(size_t)(2 * c + 1) * D + f] = S2;
+}
+
+__global__ __launch_bounds__(64) void k_obsnorm_reduce(const double *ws, const long long n_chunks, const int D,
+                                                       double *sums) {
+  const int e = blockIdx.x * 64 + threadIdx.x;
+  if (e >= 2 * D) return;
+  double T = 0.0;
+  for (long long c0 = 0; c0 < n_chunks; c0 += OBSNORM_RSTAGE) {
+    double v[OBSNORM_RSTAGE];
+#pragma unroll
+    for (int u = 0; u < OBSNORM_RSTAGE; ++u) v[u] = c0 + u < n_chunks ? ws[(size_t)(c0 + u) * 2 * D + e] : 0.0;
+#pragma unroll
+    for (int u = 0; u < OBSNORM_RSTAGE; ++u)
+      if (c0 + u < n_chunks) T = T + v[u];
+  }
+  sums[e] = T;
+}
+
+__global__ __launch_bounds__(POB_MLP_MAX_WIDTH) void k_obsnorm_update(double *count, float *table, const int D,
+                                                                      const double *sums, const int R,
+                                                                      const long long n_new) {
+  const int f = threadIdx.x;
+  const double cnt = count[0];
+  __syncthreads();  // every lane holds the old count before lane 0 replaces it
+  double total = cnt;
+  if (f < D) {
+    double S1 = 0.0, S2 = 0.0;
+    for (int r = 0; r < R; ++r) {
+      S1 = S1 + sums[(size_t)(2 * r) * D + f];
+      S2 = S2 + sums[(size_t)(2 * r + 1) * D + f];
+    }
+    float mean = table[f], scale = table[D + f], m2 = table[2 * D + f];
+    total = pob_obsnorm_finish(cnt, (double)n_new, S1, S2, mean, scale, m2);
+    table[f] = mean;
+    table[D + f] = scale;
+    table[2 * D + f] = m2;
+  }
+  if (f == 0) count[0] = total;
+}
+
+static int obsnorm_chunks(long long N, int D, long long *n_chunks) {
+  if (D < 1 || D > POB_MLP_MAX_WIDTH) return pob_fail_msg(POB_EINVAL, "obsnorm: the observation width must be in 1 .. 256");
+  if (N < 1) return pob_fail_msg(POB_EINVAL, "obsnorm: the row count must be positive");
+  if (N > (1LL << 40)) return pob_fail_msg(POB_EINVAL, "obsnorm: at most 2^40 rows");
+  *n_chunks = (N + POB_OBSNORM_CHUNK - 1) / POB_OBSNORM_CHUNK;
+  return POB_OK;
+}
+
+extern "C" {
+
+int pob_obsnorm_workspace_bytes(long long N, int D, long long *bytes) {
+  if (!bytes) return pob_fail_msg(POB_EINVAL, "obsnorm: bytes is NULL");
+  long long n_chunks;
+  const int rc = obsnorm_chunks(N, D, &n_chunks);
+  if (rc != POB_OK) return rc;
+  *bytes = n_chunks * 2 * D * (long long)sizeof(double);
+  return POB_OK;
+}
+
+int pob_obsnorm_accumulate(const float *obs, long long N, int D, const float *table, double *workspace, double *sums,
+                           void *stream) {
+  long long n_chunks;
+  const int rc = obsnorm_chunks(N, D, &n_chunks);
+  if (rc != POB_OK) return rc;
+  if (!obs || !table || !workspace || !sums) return pob_fail_msg(POB_EINVAL, "obsnorm: NULL argument (obs, table, workspace, sums)");
+  hipStream_t st = (hipStream_t)stream;
+  const long long n_items = n_chunks * D;
+  hipLaunchKernelGGL(k_obsnorm_accumulate, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, st, obs, N, D, table,
+                     workspace, n_items);
+  hipLaunchKernelGGL(k_obsnorm_reduce, dim3((unsigned)((2 * D + 63) / 64)), dim3(64), 0, st, workspace, n_chunks, D, sums);
+  return mlp_hip_check(hipGetLastError(), "k_obsnorm_accumulate launch");
+}
+
+int pob_obsnorm_update(double *count_io, float *table_io, int D, const double *sums, int R, long long n_new, void *stream) {
+  if (D < 1 || D > POB_MLP_MAX_WIDTH) return pob_fail_msg(POB_EINVAL, "obsnorm: the observation width must be in 1 .. 256");
+  if (R < 1) return pob_fail_msg(POB_EINVAL, "obsnorm: the shard count R must be positive");
+  if (n_new < 1) return pob_fail_msg(POB_EINVAL, "obsnorm: the row count must be positive");
+  if (!count_io || !table_io || !sums) return pob_fail_msg(POB_EINVAL, "obsnorm: NULL argument (count, table, sums)");
+  hipLaunchKernelGGL(k_obsnorm_update, dim3(1), dim3(POB_MLP_MAX_WIDTH), 0, (hipStream_t)stream, count_io, table_io, D, sums,
+                     R, n_new);
+  return mlp_hip_check(hipGetLastError(), "k_obsnorm_update launch");
 }
 
 }  // extern "C"

@@ -61,6 +61,8 @@ EXPORTS = (
     "pob_env_set_obs_mask",
     "pob_mlp_create", "pob_mlp_destroy", "pob_mlp_param_count", "pob_mlp_forward", "pob_policy_act",
     "pob_gru_create", "pob_gru_destroy", "pob_gru_param_count", "pob_gru_forward", "pob_gru_policy_act",
+    "pob_obsnorm_workspace_bytes", "pob_obsnorm_accumulate", "pob_obsnorm_update",
+    "pob_mlp_forward_norm", "pob_policy_act_norm", "pob_gru_forward_norm", "pob_gru_policy_act_norm",
 )
 
 
@@ -113,6 +115,13 @@ def _load():
     lib.pob_gru_forward.argtypes = [_VP, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, _VP]
     lib.pob_gru_policy_act.argtypes = [_VP, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int, _VP, _VP, _VP, _VP,
                                        _VP, _VP, _VP, _VP, _VP]
+    lib.pob_obsnorm_workspace_bytes.argtypes = [C.c_longlong, C.c_int, C.POINTER(C.c_longlong)]
+    lib.pob_obsnorm_accumulate.argtypes = [_VP, C.c_longlong, C.c_int, _VP, _VP, _VP, _VP]
+    lib.pob_obsnorm_update.argtypes = [_VP, _VP, C.c_int, _VP, C.c_int, C.c_longlong, _VP]
+    # the _norm twins: the plain argument list, then norm (3, D), norm_clip, stream
+    for name in ("pob_mlp_forward", "pob_policy_act", "pob_gru_forward", "pob_gru_policy_act"):
+        plain = getattr(lib, name).argtypes
+        getattr(lib, name + "_norm").argtypes = list(plain[:-1]) + [_VP, C.c_float, _VP]
     if lib.pob_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {lib.pob_abi_version()} != {ABI_VERSION}; rebuild it")
     for name in EXPORTS:

@@ -277,9 +277,14 @@ class ActorRollout:
         roll.reward[t], roll.done[t]                              # the step's outcome
 
     The parameters are read at replay time: ``policy.theta`` updated in place between replays
-    changes the next replay's actions.  Single-kind ``create(...)`` chains only."""
+    changes the next replay's actions.  Single-kind ``create(...)`` chains only.
 
-    def __init__(self, env, state, policy, steps: int):
+    A policy with a ``normalizer`` acts on the normalised observation (``roll.obs`` keeps the raw
+    rows).  ``update_normalizer=True`` appends the statistics update over ``roll.obs`` (T B rows)
+    as the graph's last nodes: a replay acts under the table it started with and leaves the
+    updated one for the next (brax PPO's order), with no host work in between."""
+
+    def __init__(self, env, state, policy, steps: int, update_normalizer: bool = False):
         from .training.networks import NormalTanhPolicy
         if steps <= 0:
             raise ValueError("steps must be positive")
@@ -296,6 +301,7 @@ class ActorRollout:
             raise ValueError(f"the policy maps {policy.obs_size} -> {policy.action_size}, the env {D} -> {A}")
         self.env, self.state, self.policy, self.steps = env, state, policy, int(steps)
         dev, T = obs.device, self.steps
+        self.update_normalizer = _normalizer_to_update(policy, update_normalizer, T * B)
         self.obs = torch.empty((T, B, D), dtype=torch.float32, device=dev)
         self.actions = torch.empty((T, B, A), dtype=torch.float32, device=dev)
         self.raw = torch.empty((T, B, A), dtype=torch.float32, device=dev)
@@ -310,12 +316,25 @@ class ActorRollout:
                 self.state = env.step_(self.state, self.actions[t])
                 self.reward[t].copy_(self.state.reward)
                 self.done[t].copy_(self.state.aux["done"] if "done" in self.state.aux else self.state.done)
+            if self.update_normalizer:
+                policy.normalizer.update(self.obs)
         _release_deferred()
 
     def replay(self):
         """Run the captured unroll (stream-ordered on torch's current stream)."""
         self.graph.replay()
         return self.state
+
+
+def _normalizer_to_update(policy, update_normalizer: bool, n_rows: int) -> bool:
+    """The ``update_normalizer=`` guard of the actor rollouts; sizes the update's workspace
+    before the capture."""
+    if not update_normalizer:
+        return False
+    if getattr(policy, "normalizer", None) is None:
+        raise ValueError("update_normalizer=True needs a policy constructed with normalizer=...")
+    policy.normalizer.reserve(n_rows)
+    return True
 
 
 class RecurrentActorRollout:
@@ -335,9 +354,10 @@ class RecurrentActorRollout:
 
     ``masked=True`` acts on ``state.info["obs_masked"]`` (the ``obs_mask=`` columns the step
     kernel writes) instead of ``state.obs``; ``roll.obs`` then holds those columns.
-    Single-kind ``create(...)`` chains only."""
+    Single-kind ``create(...)`` chains only.  ``update_normalizer=True``: as ``ActorRollout``
+    (with ``masked=True`` the policy's normaliser is one over the masked columns)."""
 
-    def __init__(self, env, state, policy, steps: int, masked: bool = False):
+    def __init__(self, env, state, policy, steps: int, masked: bool = False, update_normalizer: bool = False):
         from .training.networks import RecurrentTanhPolicy
         if steps <= 0:
             raise ValueError("steps must be positive")
@@ -358,6 +378,7 @@ class RecurrentActorRollout:
         self.env, self.state, self.policy, self.steps = env, state, policy, int(steps)
         dev, T = obs.device, self.steps
         policy._buffers(B)  # hidden and reset exist before the capture
+        self.update_normalizer = _normalizer_to_update(policy, update_normalizer, T * B)
         self.obs = torch.empty((T, B, D), dtype=torch.float32, device=dev)
         self.actions = torch.empty((T, B, A), dtype=torch.float32, device=dev)
         self.raw = torch.empty((T, B, A), dtype=torch.float32, device=dev)
@@ -375,6 +396,8 @@ class RecurrentActorRollout:
                 self.reward[t].copy_(self.state.reward)
                 self.done[t].copy_(self.state.aux["done"] if "done" in self.state.aux else self.state.done)
             policy.reset.copy_(self.done[T - 1])
+            if self.update_normalizer:
+                policy.normalizer.update(self.obs)
         _release_deferred()
 
     def _obs_of(self, state):

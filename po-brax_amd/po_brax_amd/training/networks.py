@@ -14,6 +14,10 @@ networks".
 ``make_recurrent_model`` / ``RecurrentTanhPolicy`` are the recurrent counterparts (pre-MLP ->
 GRU cell -> post-MLP, ``pob_gru_forward`` / ``pob_gru_policy_act``, the hidden state carried on
 the device), unrolled by ``rollout.RecurrentActorRollout``: DESIGN.md "Recurrent actor".
+
+Both policies take ``normalizer=`` (``normalization.ObservationNormalizer``): the running
+observation normaliser applied inside the actor kernel's tile load (``pob_*_policy_act_norm``):
+DESIGN.md "Observation normaliser".
 """
 from __future__ import annotations
 
@@ -26,6 +30,7 @@ import torch
 
 from .. import _lib
 from .._lib import check, lib, ptr
+from . import normalization as _normalization
 
 ACTIVATIONS = {"relu": 0, "swish": 1, "silu": 1, "tanh": 2}
 _TORCH_ACT = {0: torch.relu, 1: torch.nn.functional.silu, 2: torch.tanh}
@@ -396,10 +401,13 @@ class RecurrentTanhPolicy:
     thread key advance.  The policy owns ``hidden`` (B, H), carried in place from call to call,
     and ``reset`` (B,): where it is non-zero the env starts the next call from h = 0 (write the
     env's ``done`` into it).  Both are allocated at first use and start as zeros; after that no
-    allocation, no host sync: capture-safe."""
+    allocation, no host sync: capture-safe.  ``normalizer`` (a ``normalization.ObservationNormalizer``
+    of the observation's width -- the masked columns' when the policy acts on those): the network
+    sees the normalised observation (``pob_gru_policy_act_norm``, its table read at launch time);
+    ``obs_copy`` keeps the raw rows and the hidden state is never normalised."""
 
     def __init__(self, model: RecurrentModel, params: RecurrentParams, key, total: Optional[int] = None, first: int = 0,
-                 deterministic: bool = False):
+                 deterministic: bool = False, normalizer=None):
         if model.gru is None:
             raise ValueError("model must come from make_recurrent_model")
         if model.post_sizes[-1] % 2:
@@ -412,6 +420,7 @@ class RecurrentTanhPolicy:
         self.model, self.params, self.theta = model, params, theta
         self.obs_size, self.action_size = model.pre_sizes[0], model.post_sizes[-1] // 2
         self.hidden_size = model.hidden_size
+        self.normalizer = _normalization.attach(normalizer, self.obs_size, theta.device)
         self.key = _key_words(key).to(theta.device).clone()
         self.total, self.first = (None if total is None else int(total)), int(first)
         self.deterministic = bool(deterministic)
@@ -443,9 +452,14 @@ class RecurrentTanhPolicy:
                                       and t.device == obs.device):
                 raise ValueError(f"buffer must be a contiguous float32 tensor {shape} on {obs.device}")
         total = B if self.total is None else self.total
-        check(lib.pob_gru_policy_act(self.model.gru.handle, B, total, self.first, ptr(obs), ptr(self.theta), ptr(self.key),
-                                     int(self.deterministic), ptr(reset), ptr(self.hidden), ptr(action), ptr(logp),
-                                     ptr(raw), ptr(logits), ptr(obs_copy), ptr(hidden_in), _lib.stream_handle(obs.device)))
+        args = (self.model.gru.handle, B, total, self.first, ptr(obs), ptr(self.theta), ptr(self.key),
+                int(self.deterministic), ptr(reset), ptr(self.hidden), ptr(action), ptr(logp), ptr(raw), ptr(logits),
+                ptr(obs_copy), ptr(hidden_in))
+        if self.normalizer is None:
+            check(lib.pob_gru_policy_act(*args, _lib.stream_handle(obs.device)))
+        else:
+            check(lib.pob_gru_policy_act_norm(*args, ptr(self.normalizer.table), self.normalizer.clip,
+                                              _lib.stream_handle(obs.device)))
         return action
 
     def __call__(self, obs: torch.Tensor) -> torch.Tensor:
@@ -461,10 +475,13 @@ class NormalTanhPolicy:
     the last call's log-probability and pre-tanh action; ``deterministic = True`` gives
     ``tanh(loc)`` and leaves the key and ``.logp`` alone.  The noise of env ``b`` is row
     ``first + b`` of a draw for ``total`` envs, so a shard's actions equal the slice of the
-    whole batch's."""
+    whole batch's.  ``normalizer`` (a ``normalization.ObservationNormalizer`` of width ``obs_size``):
+    the network sees ``normalizer.apply(obs)``, computed in the tile load (``pob_policy_act_norm``,
+    the table read at launch time: an update between replays changes the next replay's actions);
+    ``obs_copy`` keeps the raw rows."""
 
     def __init__(self, model: FeedForwardModel, params: Params, key, total: Optional[int] = None, first: int = 0,
-                 deterministic: bool = False):
+                 deterministic: bool = False, normalizer=None):
         if model.mlp is None or model.layer_sizes is None:
             raise ValueError("model must come from make_model")
         if model.layer_sizes[-1] % 2:
@@ -476,6 +493,7 @@ class NormalTanhPolicy:
             raise ValueError(f"theta has {theta.numel()} elements, the network {model.mlp.param_count}")
         self.model, self.params, self.theta = model, params, theta
         self.obs_size, self.action_size = model.layer_sizes[0], model.layer_sizes[-1] // 2
+        self.normalizer = _normalization.attach(normalizer, self.obs_size, theta.device)
         self.key = _key_words(key).to(theta.device).clone()
         self.total, self.first = (None if total is None else int(total)), int(first)
         self.deterministic = bool(deterministic)
@@ -499,9 +517,13 @@ class NormalTanhPolicy:
                                       and t.device == obs.device):
                 raise ValueError(f"output buffer must be a contiguous float32 tensor {shape} on {obs.device}")
         total = B if self.total is None else self.total
-        check(lib.pob_policy_act(self.model.mlp.handle, B, total, self.first, ptr(obs), ptr(self.theta), ptr(self.key),
-                                 int(self.deterministic), ptr(action), ptr(logp), ptr(raw), ptr(logits), ptr(obs_copy),
-                                 _lib.stream_handle(obs.device)))
+        args = (self.model.mlp.handle, B, total, self.first, ptr(obs), ptr(self.theta), ptr(self.key),
+                int(self.deterministic), ptr(action), ptr(logp), ptr(raw), ptr(logits), ptr(obs_copy))
+        if self.normalizer is None:
+            check(lib.pob_policy_act(*args, _lib.stream_handle(obs.device)))
+        else:
+            check(lib.pob_policy_act_norm(*args, ptr(self.normalizer.table), self.normalizer.clip,
+                                          _lib.stream_handle(obs.device)))
         return action
 
     def __call__(self, obs: torch.Tensor) -> torch.Tensor:

@@ -23,6 +23,16 @@ no pre-MLP, one post layer of 2 A logits):
 
 --masked creates the envs with the standard observability mask (30 of HH's 114 columns, fused
 into the step kernel) and both policies act on state.info["obs_masked"].
+
+--normalize replaces leg A by two more native legs (with --recurrent the recurrent actor's):
+
+  N  leg B's rollout whose policy carries an ObservationNormalizer (the table applied in the
+     actor kernel's tile load)
+  U  leg N with update_normalizer=True: the statistics update over the replay's T B observation
+     rows as the graph's last nodes
+
+and times normalizer.update(roll.obs) on its own; the JSON then holds the actor's share with
+and without the table, the update per replay (U - N and alone) and its HBM time at 8 TB/s.
 """
 import argparse
 import json
@@ -105,6 +115,7 @@ def main():
     ap.add_argument("--recurrent", action="store_true")
     ap.add_argument("--masked", action="store_true")
     ap.add_argument("--hidden", type=int, default=64)
+    ap.add_argument("--normalize", action="store_true")
     args = ap.parse_args()
 
     from po_brax_amd import envs, jumpy
@@ -119,11 +130,28 @@ def main():
             ap.error("--masked goes with --recurrent")
         from po_brax_amd import standard_observability_masks as M
         mask = M.po_env_mask(args.env, cfrc=False)
-    es = [envs.create(args.env, batch_size=B, obs_mask=mask) for _ in range(3)]
+    es = [envs.create(args.env, batch_size=B, obs_mask=mask) for _ in range(4 if args.normalize else 3)]
     ss = [e.reset(keys) for e in es]
     A, D = es[0].action_size, es[0].observation_size
     if args.recurrent:
         D = es[0].masked_observation_size if args.masked else D
+    if args.normalize:
+        from po_brax_amd.training.normalization import ObservationNormalizer
+        norms = [None, ObservationNormalizer(D), ObservationNormalizer(D)]
+        legs = {}
+        for i, (leg, upd) in enumerate((("B", False), ("N", False), ("U", True))):
+            if args.recurrent:
+                model = networks.make_recurrent_model([], args.hidden, [2 * A], D)
+                pol = networks.RecurrentTanhPolicy(model, model.init(jumpy.random_prngkey(1)), jumpy.random_prngkey(2),
+                                                   normalizer=norms[i])
+                legs[leg] = RecurrentActorRollout(es[i], ss[i], pol, T, masked=args.masked, update_normalizer=upd)
+            else:
+                model = networks.make_models(2 * A, D)[0]
+                pol = networks.NormalTanhPolicy(model, model.init(jumpy.random_prngkey(1)), jumpy.random_prngkey(2),
+                                                normalizer=norms[i])
+                legs[leg] = ActorRollout(es[i], ss[i], pol, T, update_normalizer=upd)
+        roll_a, roll_b = None, legs["B"]
+    elif args.recurrent:
         model = networks.make_recurrent_model([], args.hidden, [2 * A], D)
         params = model.init(jumpy.random_prngkey(1))
         torch_policy = TorchRecurrentPolicy(model, params, B, A, args.masked)
@@ -138,8 +166,15 @@ def main():
             roll_a = PolicyRollout(es[0], ss[0], TorchNormalTanhPolicy(params, A), T)
         roll_b = ActorRollout(es[1], ss[1], networks.NormalTanhPolicy(model, params, jumpy.random_prngkey(2)), T)
     acts = torch.rand((T, B, A), device="cuda") * 2 - 1
-    roll_c = GraphRollout(es[2], ss[2], acts, warmup=True)
+    roll_c = GraphRollout(es[-1], ss[-1], acts, warmup=True)
     rolls = {"A": roll_a, "B": roll_b, "C": roll_c}
+    if args.normalize:
+        rolls = {"B": legs["B"], "N": legs["N"], "U": legs["U"], "C": roll_c}
+
+        class UpdateAlone:  # normalizer.update(roll.obs) outside the graph, timed like a replay
+            def replay(self):
+                norms[1].update(legs["N"].obs)
+        rolls["update"] = UpdateAlone()
 
     def timed(roll):
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -157,6 +192,29 @@ def main():
         for k, r in rolls.items():
             ms[k].append(timed(r))
     med = {k: statistics.median(v) for k, v in ms.items()}
+    if args.normalize:
+        n_bytes = T * B * D * 4
+        res = {
+            "bench": "policy_bench", "normalize": True, "recurrent": args.recurrent, "masked": args.masked, "obs_width": D,
+            "hidden": args.hidden if args.recurrent else None, "env": args.env, "batch": B, "steps": T, "rounds": args.rounds,
+            "device": torch.cuda.get_device_name(0),
+            "B_actor_ms_per_step": round(med["B"], 5), "N_actor_table_ms_per_step": round(med["N"], 5),
+            "U_actor_table_update_ms_per_step": round(med["U"], 5), "C_graph_rollout_ms_per_step": round(med["C"], 5),
+            "actor_share_ms": round(med["B"] - med["C"], 5), "actor_share_table_ms": round(med["N"] - med["C"], 5),
+            "update_in_graph_us_per_replay": round((med["U"] - med["N"]) * T * 1e3, 2),
+            "update_alone_us": round(med["update"] * T * 1e3, 2),
+            "update_alone_min_us": round(min(ms["update"]) * T * 1e3, 2),
+            "update_bytes": n_bytes, "update_hbm_us_at_8TBs": round(n_bytes / 8e12 * 1e6, 2),
+            "min_ms_per_step": {k: round(min(v), 5) for k, v in ms.items()},
+            "max_ms_per_step": {k: round(max(v), 5) for k, v in ms.items()},
+        }
+        line = json.dumps(res)
+        print(line)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        return
     res = {
         "bench": "policy_bench", "recurrent": args.recurrent, "masked": args.masked,
         "obs_width": D, "hidden": args.hidden if args.recurrent else None, "env": args.env, "batch": B, "steps": T, "rounds": args.rounds,
