@@ -297,6 +297,20 @@ int pob_gru_policy_act_norm(const pob_gru *g, int B, int total, int first, const
                             float *logp, float *raw, float *logits, float *obs_copy, float *h_in_copy, const float *norm,
                             float norm_clip, void *stream);
 
+/* ---- generalised advantage estimation (ABI v8, additive): brax v1 PPO's compute_gae [ext] in one
+ * launch, gae_ref of csrc/pob_mlp.h bit for bit (DESIGN.md "Critic pass and GAE": formula and
+ * operation order).  All arrays row-major (T, B) float32 device memory, bootstrap (B); each env
+ * on its own, t descending from T - 1 with acc = +0, v_next = vs_next = bootstrap[b]:
+ *   m = 1 - truncation (NULL: 1);  term = done_input ? second m : second;  g = discount (1 - term)
+ *   r = reward reward_scale;  delta = (fmaf(g, v_next, r) - v) m;  adv = (fmaf(g, vs_next, r) - v) m
+ *   acc = fmaf((g m) lambda, acc, delta);  vs = acc + v;  vs_next = vs;  v_next = v
+ * second is termination when done_input == 0 and done otherwise.  vs or advantages may be NULL
+ * (not both); outputs must not overlap inputs.  T >= 1, B >= 1.  No allocation, no
+ * synchronisation: capturable. */
+int pob_gae(int T, long long B, const float *truncation /* may be NULL */, const float *second, int done_input,
+            const float *reward, float reward_scale, const float *values, const float *bootstrap, float lambda,
+            float discount, float *vs /* may be NULL */, float *advantages /* may be NULL */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

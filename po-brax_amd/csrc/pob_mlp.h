@@ -1,7 +1,8 @@
 // pob_mlp.h -- the scalar math and the plain-C restatement of the policy-network kernels
-// (pob_mlp.hip: k_mlp_forward, k_policy_act, and the recurrent k_gru_forward, k_gru_policy_act).
+// (pob_mlp.hip: k_mlp_forward, k_policy_act, the recurrent k_gru_forward, k_gru_policy_act, the
+// observation normaliser's k_obsnorm_* and k_gae).
 // Compiled for the device by hipcc and, with POB_MLP_HOST, for the host by g++
-// (tests/host/mlp_host.cpp, gru_host.cpp); both with -ffp-contract=off.
+// (tests/host/mlp_host.cpp, gru_host.cpp, obsnorm_host.cpp, gae_host.cpp); both with -ffp-contract=off.
 //
 // Every function is a fixed sequence of float32 +, *, fmaf, integer bit operations, and the
 // correctly rounded reciprocal and square root (pob_rcp / pob_sqrt of pob_math.h on the device,
@@ -215,7 +216,46 @@ POB_MLP_D double pob_obsnorm_finish(const double count, const double n_new, cons
   return total;
 }
 
+// ---------------------------------------------------------------------------- GAE
+// One step of brax v1 PPO's compute_gae [ext] for one env, t descending (DESIGN.md "Critic pass
+// and GAE"): deltas = (r + g v_{t+1} - v) m, acc = delta + g m lambda acc, vs = acc + v, adv =
+// (r + g vs_{t+1} - v) m with g = discount (1 - term), m = 1 - truncation, in ONE reverse pass.
+// Carried per env: acc (from +0), v_next and vs_next (both from the bootstrap value).  second is
+// termination, or done when done_input (then term = done m).  No special cases: a NaN stays NaN.
+#define POB_GAE_CHUNK 8  // steps whose rows k_gae loads ahead of their use
+POB_MLP_D void pob_gae_step(const float trunc, const float second, const int done_input, const float reward,
+                            const float reward_scale, const float v, const float lambda, const float discount, float &acc,
+                            float &v_next, float &vs_next, float &adv) {
+  const float m = 1.0f - trunc;
+  const float term = done_input ? second * m : second;
+  const float g = discount * (1.0f - term);
+  const float r = reward * reward_scale;
+  const float delta = (MLP_FMA(g, v_next, r) - v) * m;
+  adv = (MLP_FMA(g, vs_next, r) - v) * m;
+  acc = MLP_FMA((g * m) * lambda, acc, delta);
+  vs_next = acc + v;
+  v_next = v;
+}
+
 #ifdef POB_MLP_HOST
+// vs, advantages (T, B) of truncation (NULL: zeros), second, reward, values (T, B) row-major and
+// bootstrap (B); either output may be NULL.  Each env on its own, t descending from T - 1.
+static inline void gae_ref(const int T, const long long B, const float *truncation, const float *second,
+                           const int done_input, const float *reward, const float reward_scale, const float *values,
+                           const float *bootstrap, const float lambda, const float discount, float *vs, float *advantages) {
+  for (long long b = 0; b < B; ++b) {
+    float acc = 0.0f, v_next = bootstrap[b], vs_next = bootstrap[b];
+    for (int t = T - 1; t >= 0; --t) {
+      const long long i = (long long)t * B + b;
+      float adv;
+      pob_gae_step(truncation ? truncation[i] : 0.0f, second[i], done_input, reward[i], reward_scale, values[i], lambda,
+                   discount, acc, v_next, vs_next, adv);
+      if (advantages) advantages[i] = adv;
+      if (vs) vs[i] = vs_next;
+    }
+  }
+}
+
 // sums (2, D) float64 of x (N, D) against table row 0 (mean): rows cut into chunks of
 // POB_OBSNORM_CHUNK, a chunk's pair per column from +0.0 in ascending row order, the chunk
 // partials added per column in ascending chunk order from +0.0.  The order depends on N and D only.

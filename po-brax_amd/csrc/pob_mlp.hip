@@ -739,3 +739,87 @@ int pob_obsnorm_update(double *count_io, float *table_io, int D, const double *s
 }
 
 }  // extern "C"
+
+// ============================================================================ GAE
+// gae_ref of pob_mlp.h (the specification; DESIGN.md "Critic pass and GAE").  One lane per env,
+// consecutive lanes on consecutive b (every load and store a coalesced row segment), t
+// descending.  The carried chain is pob_gae_step's fmaf and add; the loads do not depend on it,
+// so the steps are taken in chunks of POB_GAE_CHUNK whose rows are all issued before the chunk
+// before them is consumed (two register images: at one or two waves per CU the loop then waits
+// for HBM once per chunk, not once per step).  The newest chunk takes the (T - 1) % POB_GAE_CHUNK
+// + 1 steps that make every later chunk a full one.  TRUNC = false: truncation is NULL (m = 1 - 0).
+// No LDS, no atomics, no scratch.
+struct gae_rows { float tr[POB_GAE_CHUNK], se[POB_GAE_CHUNK], rw[POB_GAE_CHUNK], va[POB_GAE_CHUNK]; };
+
+// rows t_hi, t_hi - 1, .., t_hi - POB_GAE_CHUNK + 1 of lane b; a row before the first (the newest
+// chunk of a T that is no multiple of the chunk) is loaded as row 0 and never used
+template <bool TRUNC>
+__device__ __forceinline__ void gae_load(gae_rows &r, const int t_hi, const size_t B, const size_t b,
+                                         const float *truncation, const float *second, const float *reward,
+                                         const float *values) {
+#pragma unroll
+  for (int u = 0; u < POB_GAE_CHUNK; ++u) {
+    const size_t i = (size_t)(t_hi - u > 0 ? t_hi - u : 0) * B + b;
+    r.tr[u] = TRUNC ? truncation[i] : 0.0f;
+    r.se[u] = second[i];
+    r.rw[u] = reward[i];
+    r.va[u] = values[i];
+  }
+}
+
+template <bool TRUNC>
+__global__ __launch_bounds__(64) void k_gae(const int T, const long long B, const float *truncation, const float *second,
+                                            const int done_input, const float *reward, const float reward_scale,
+                                            const float *values, const float *bootstrap, const float lambda,
+                                            const float discount, float *vs, float *advantages) {
+  const long long lane = (long long)blockIdx.x * 64 + threadIdx.x;
+  if (lane >= B) return;
+  const size_t b = (size_t)lane, Bs = (size_t)B;
+  float acc = 0.0f, v_next = bootstrap[b], vs_next = v_next;
+  int t = T - 1;                          // the chunk in `cur` is steps t, t - 1, .., t - n + 1
+  int n = (T - 1) % POB_GAE_CHUNK + 1;
+  gae_rows cur, nxt;
+  gae_load<TRUNC>(cur, t, Bs, b, truncation, second, reward, values);
+  for (;;) {
+    const bool more = t - n >= 0;  // then t - n + 1 is a multiple of the chunk: a full chunk follows
+    if (more) gae_load<TRUNC>(nxt, t - n, Bs, b, truncation, second, reward, values);
+#pragma unroll
+    for (int u = 0; u < POB_GAE_CHUNK; ++u)
+      if (u < n) {
+        float adv;
+        pob_gae_step(cur.tr[u], cur.se[u], done_input, cur.rw[u], reward_scale, cur.va[u], lambda, discount, acc, v_next,
+                     vs_next, adv);
+        const size_t i = (size_t)(t - u) * Bs + b;
+        if (advantages) advantages[i] = adv;
+        if (vs) vs[i] = vs_next;
+      }
+    if (!more) break;
+    t -= n;
+    n = POB_GAE_CHUNK;
+    cur = nxt;
+  }
+}
+
+extern "C" {
+
+int pob_gae(int T, long long B, const float *truncation, const float *second, int done_input, const float *reward,
+            float reward_scale, const float *values, const float *bootstrap, float lambda, float discount, float *vs,
+            float *advantages, void *stream) {
+  if (T < 1) return pob_fail_msg(POB_EINVAL, "gae: the step count T must be positive");
+  if (B < 1) return pob_fail_msg(POB_EINVAL, "gae: the batch size B must be positive");
+  if (B > (1LL << 36)) return pob_fail_msg(POB_EINVAL, "gae: at most 2^36 envs");
+  if (!second || !reward || !values || !bootstrap)
+    return pob_fail_msg(POB_EINVAL, "gae: NULL argument (second, reward, values, bootstrap)");
+  if (!vs && !advantages) return pob_fail_msg(POB_EINVAL, "gae: vs and advantages are both NULL");
+  const dim3 grid((unsigned)((B + 63) / 64));
+  hipStream_t st = (hipStream_t)stream;
+  if (truncation)
+    hipLaunchKernelGGL(k_gae<true>, grid, dim3(64), 0, st, T, B, truncation, second, done_input ? 1 : 0, reward,
+                       reward_scale, values, bootstrap, lambda, discount, vs, advantages);
+  else
+    hipLaunchKernelGGL(k_gae<false>, grid, dim3(64), 0, st, T, B, truncation, second, done_input ? 1 : 0, reward,
+                       reward_scale, values, bootstrap, lambda, discount, vs, advantages);
+  return mlp_hip_check(hipGetLastError(), "k_gae launch");
+}
+
+}  // extern "C"

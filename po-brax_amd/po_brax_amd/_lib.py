@@ -63,6 +63,7 @@ EXPORTS = (
     "pob_gru_create", "pob_gru_destroy", "pob_gru_param_count", "pob_gru_forward", "pob_gru_policy_act",
     "pob_obsnorm_workspace_bytes", "pob_obsnorm_accumulate", "pob_obsnorm_update",
     "pob_mlp_forward_norm", "pob_policy_act_norm", "pob_gru_forward_norm", "pob_gru_policy_act_norm",
+    "pob_gae",
 )
 
 
@@ -122,6 +123,9 @@ def _load():
     for name in ("pob_mlp_forward", "pob_policy_act", "pob_gru_forward", "pob_gru_policy_act"):
         plain = getattr(lib, name).argtypes
         getattr(lib, name + "_norm").argtypes = list(plain[:-1]) + [_VP, C.c_float, _VP]
+    # T, B, truncation, second, done_input, reward, reward_scale, values, bootstrap, lambda, discount, vs, adv, stream
+    lib.pob_gae.argtypes = [C.c_int, C.c_longlong, _VP, _VP, C.c_int, _VP, C.c_float, _VP, _VP, C.c_float, C.c_float,
+                            _VP, _VP, _VP]
     if lib.pob_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {lib.pob_abi_version()} != {ABI_VERSION}; rebuild it")
     for name in EXPORTS:

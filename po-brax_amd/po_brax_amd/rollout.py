@@ -282,9 +282,19 @@ class ActorRollout:
     A policy with a ``normalizer`` acts on the normalised observation (``roll.obs`` keeps the raw
     rows).  ``update_normalizer=True`` appends the statistics update over ``roll.obs`` (T B rows)
     as the graph's last nodes: a replay acts under the table it started with and leaves the
-    updated one for the next (brax PPO's order), with no host work in between."""
+    updated one for the next (brax PPO's order), with no host work in between.
 
-    def __init__(self, env, state, policy, steps: int, update_normalizer: bool = False):
+    ``critic=training.gae.ValueFunction(...)`` appends the critic pass (DESIGN.md "Critic pass and
+    GAE"): the observation buffer gains a row ``T`` (``roll.final_obs``, the last state's
+    observation; ``roll.obs`` stays the (T, B, D) view), every step records ``roll.truncation[t]``,
+    and after the normaliser update the graph ends with one value launch over all (T + 1) B rows
+    into ``roll.values`` (T + 1, B) and one ``pob_gae`` launch into ``roll.vs`` and
+    ``roll.advantages`` (T, B), bootstrapped from ``values[T]``; ``gae=dict(lambda_=, discount=,
+    reward_scaling=)`` over ``compute_gae``'s defaults.  ``record_truncation=True`` records
+    ``roll.truncation`` without a critic."""
+
+    def __init__(self, env, state, policy, steps: int, update_normalizer: bool = False, critic=None, gae=None,
+                 record_truncation: bool = False):
         from .training.networks import NormalTanhPolicy
         if steps <= 0:
             raise ValueError("steps must be positive")
@@ -302,7 +312,7 @@ class ActorRollout:
         self.env, self.state, self.policy, self.steps = env, state, policy, int(steps)
         dev, T = obs.device, self.steps
         self.update_normalizer = _normalizer_to_update(policy, update_normalizer, T * B)
-        self.obs = torch.empty((T, B, D), dtype=torch.float32, device=dev)
+        self.obs = _critic_buffers(self, critic, gae, record_truncation, state, T, B, D, dev)
         self.actions = torch.empty((T, B, A), dtype=torch.float32, device=dev)
         self.raw = torch.empty((T, B, A), dtype=torch.float32, device=dev)
         self.logp = torch.zeros((T, B), dtype=torch.float32, device=dev)
@@ -316,8 +326,12 @@ class ActorRollout:
                 self.state = env.step_(self.state, self.actions[t])
                 self.reward[t].copy_(self.state.reward)
                 self.done[t].copy_(self.state.aux["done"] if "done" in self.state.aux else self.state.done)
+                _record_truncation(self, t)
+            if self.critic is not None:
+                self.final_obs.copy_(self.state.obs)
             if self.update_normalizer:
                 policy.normalizer.update(self.obs)
+            _critic_pass(self)
         _release_deferred()
 
     def replay(self):
@@ -335,6 +349,60 @@ def _normalizer_to_update(policy, update_normalizer: bool, n_rows: int) -> bool:
         raise ValueError("update_normalizer=True needs a policy constructed with normalizer=...")
     policy.normalizer.reserve(n_rows)
     return True
+
+
+def _critic_buffers(roll, critic, gae, record_truncation: bool, state, T: int, B: int, D: int, dev) -> torch.Tensor:
+    """The ``critic=``, ``gae=``, ``record_truncation=`` arguments of the actor rollouts: checks
+    them, allocates what they add to the trajectory and returns the (T, B, D) observation rows --
+    with a critic the first T of a (T + 1, B, D) buffer whose last is ``roll.final_obs``."""
+    f = dict(dtype=torch.float32, device=dev)
+    roll.critic = critic
+    if critic is None and gae is not None:
+        raise ValueError("gae= needs critic=")
+    if critic is not None:
+        from .training.gae import ValueFunction, gae_options
+        if not isinstance(critic, ValueFunction):
+            raise TypeError("critic must be a training.gae.ValueFunction")
+        if critic.obs_size != D:
+            raise ValueError(f"the critic is for observations of width {critic.obs_size}, the rollout records {D}")
+        if critic.theta.device != dev:
+            raise ValueError(f"the critic is on {critic.theta.device}, the rollout on {dev}")
+        if (T + 1) * B >= 2 ** 31:
+            raise ValueError("the critic pass takes fewer than 2^31 observation rows")
+        roll.gae = gae_options(gae)
+    if critic is not None or record_truncation:
+        roll._truncation_source = "truncation" in state.aux
+        # an env without a time limit never truncates: zeros, set once
+        roll.truncation = (torch.empty if roll._truncation_source else torch.zeros)((T, B), **f)
+    if critic is None:
+        return torch.empty((T, B, D), **f)
+    roll._obs_buffer = torch.empty((T + 1, B, D), **f)
+    roll.final_obs = roll._obs_buffer[T]
+    roll.values = torch.empty((T + 1, B), **f)
+    roll.vs = torch.empty((T, B), **f)
+    roll.advantages = torch.empty((T, B), **f)
+    return roll._obs_buffer[:T]
+
+
+def _record_truncation(roll, t: int) -> None:
+    """Step t's truncation row, from the engine's float32 buffer of the state just stepped."""
+    if getattr(roll, "_truncation_source", False):
+        roll.truncation[t].copy_(roll.state.aux["truncation"])
+
+
+def _critic_pass(roll) -> None:
+    """The graph's last nodes with a critic: the values of all (T + 1) B recorded rows in one
+    launch, then ``pob_gae`` on the trajectory's ``done`` (done_input = 1)."""
+    if roll.critic is None:
+        return
+    from . import _lib
+    T, B = roll.steps, int(roll.values.shape[1])
+    roll.critic.values_into(roll._obs_buffer.view((T + 1) * B, -1), roll.values.view(-1))
+    o = roll.gae
+    _lib.check(_lib.lib.pob_gae(T, B, _lib.ptr(roll.truncation), _lib.ptr(roll.done), 1, _lib.ptr(roll.reward),
+                                o["reward_scaling"], _lib.ptr(roll.values), _lib.ptr(roll.values[T]), o["lambda_"],
+                                o["discount"], _lib.ptr(roll.vs), _lib.ptr(roll.advantages),
+                                _lib.stream_handle(roll.values.device)))
 
 
 class RecurrentActorRollout:
@@ -355,9 +423,12 @@ class RecurrentActorRollout:
     ``masked=True`` acts on ``state.info["obs_masked"]`` (the ``obs_mask=`` columns the step
     kernel writes) instead of ``state.obs``; ``roll.obs`` then holds those columns.
     Single-kind ``create(...)`` chains only.  ``update_normalizer=True``: as ``ActorRollout``
-    (with ``masked=True`` the policy's normaliser is one over the masked columns)."""
+    (with ``masked=True`` the policy's normaliser is one over the masked columns).  ``critic=``,
+    ``gae=``, ``record_truncation=``: as ``ActorRollout``; the critic is feed-forward, of the
+    recorded observation's width (the masked columns' with ``masked=True``)."""
 
-    def __init__(self, env, state, policy, steps: int, masked: bool = False, update_normalizer: bool = False):
+    def __init__(self, env, state, policy, steps: int, masked: bool = False, update_normalizer: bool = False,
+                 critic=None, gae=None, record_truncation: bool = False):
         from .training.networks import RecurrentTanhPolicy
         if steps <= 0:
             raise ValueError("steps must be positive")
@@ -379,7 +450,7 @@ class RecurrentActorRollout:
         dev, T = obs.device, self.steps
         policy._buffers(B)  # hidden and reset exist before the capture
         self.update_normalizer = _normalizer_to_update(policy, update_normalizer, T * B)
-        self.obs = torch.empty((T, B, D), dtype=torch.float32, device=dev)
+        self.obs = _critic_buffers(self, critic, gae, record_truncation, state, T, B, D, dev)
         self.actions = torch.empty((T, B, A), dtype=torch.float32, device=dev)
         self.raw = torch.empty((T, B, A), dtype=torch.float32, device=dev)
         self.logp = torch.zeros((T, B), dtype=torch.float32, device=dev)
@@ -395,9 +466,13 @@ class RecurrentActorRollout:
                 self.state = env.step_(self.state, self.actions[t])
                 self.reward[t].copy_(self.state.reward)
                 self.done[t].copy_(self.state.aux["done"] if "done" in self.state.aux else self.state.done)
+                _record_truncation(self, t)
             policy.reset.copy_(self.done[T - 1])
+            if self.critic is not None:
+                self.final_obs.copy_(self._obs_of(self.state))
             if self.update_normalizer:
                 policy.normalizer.update(self.obs)
+            _critic_pass(self)
         _release_deferred()
 
     def _obs_of(self, state):
