@@ -311,6 +311,24 @@ int pob_gae(int T, long long B, const float *truncation /* may be NULL */, const
             const float *reward, float reward_scale, const float *values, const float *bootstrap, float lambda,
             float discount, float *vs /* may be NULL */, float *advantages /* may be NULL */, void *stream);
 
+/* ---- PPO loss on the tanh-normal head (ABI v8, additive): brax v1 ppo.compute_ppo_loss [ext] and
+ * its gradient to the logits and the values, ppo_loss_ref of csrc/pob_mlp.h bit for bit (DESIGN.md
+ * "PPO loss": formula, operation and summation order).  logits (M, 2 A) and values (M) are in
+ * minibatch order; raw (N, A), old_logp, advantages, vs (N) in trajectory order: row i reads
+ * trajectory row idx[i] (every entry in [0, N): not checked), or row i when idx is NULL.  The
+ * entropy is sampled with u = uniform(split(key)[1], (M, A), -1, 1) of the device threefry; the
+ * key is read, never advanced.  losses[4] = total, policy_loss, value_loss, entropy_loss; dlogits
+ * (M, 2 A) and dvalues (M) = d total / d logits, d total / d values, either may be NULL.
+ * workspace: pob_ppo_loss_workspace_bytes(M) bytes; it starts with the (ceil(M / 1024), 3) float64
+ * chunk partials of the three sums.  1 <= A <= 128, M A < 2^32 - 1.  Arguments are checked before
+ * any HIP call; no allocation, no synchronisation: capturable. */
+int pob_ppo_loss_workspace_bytes(long long M, long long *bytes);
+int pob_ppo_loss(long long M, int A, const float *logits, const float *values, const int32_t *idx /* may be NULL */,
+                 const float *raw, const float *old_logp, const float *advantages, const float *vs,
+                 const uint32_t *key, float entropy_cost, float ppo_epsilon,
+                 float *dlogits /* may be NULL */, float *dvalues /* may be NULL */, float *losses /* 4 */,
+                 double *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,8 +1,9 @@
 // pob_mlp.h -- the scalar math and the plain-C restatement of the policy-network kernels
 // (pob_mlp.hip: k_mlp_forward, k_policy_act, the recurrent k_gru_forward, k_gru_policy_act, the
-// observation normaliser's k_obsnorm_* and k_gae).
+// observation normaliser's k_obsnorm_*, k_gae and k_ppo_*).
 // Compiled for the device by hipcc and, with POB_MLP_HOST, for the host by g++
-// (tests/host/mlp_host.cpp, gru_host.cpp, obsnorm_host.cpp, gae_host.cpp); both with -ffp-contract=off.
+// (tests/host/mlp_host.cpp, gru_host.cpp, obsnorm_host.cpp, gae_host.cpp, ppo_host.cpp); both with
+// -ffp-contract=off.
 //
 // Every function is a fixed sequence of float32 +, *, fmaf, integer bit operations, and the
 // correctly rounded reciprocal and square root (pob_rcp / pob_sqrt of pob_math.h on the device,
@@ -237,7 +238,118 @@ POB_MLP_D void pob_gae_step(const float trunc, const float second, const int don
   v_next = v;
 }
 
+// ---------------------------------------------------------------------------- PPO loss
+// brax v1 ppo.compute_ppo_loss [ext] on the tanh-normal head, with its gradient to the logits and
+// the values (DESIGN.md "PPO loss").  One action component: the log-probability term of the STORED
+// pre-tanh action x (the noise e re-derived from it; constants and term spelling of
+// pob_tanh_normal), the sampled-entropy term from the draw u (clamped like the head's), and the
+// factors of both terms' derivatives: d term / d loc = dlp_loc, d term / d scale = dlp_sc, d ent /
+// d loc = den_loc, d ent / d scale = den_sc, d scale / d p = sig.
+#define POB_PPO_MAX_A 128             // action components: the logits' width 2 A is a legal network width
+#define POB_PPO_CHUNK POB_OBSNORM_CHUNK  // rows of one chunk of the scalars' summation order
+POB_MLP_D void pob_ppo_component(const float loc, const float p, const float x, float u, float &term, float &ent,
+                                 float &dlp_loc, float &dlp_sc, float &den_loc, float &den_sc, float &sig) {
+  const float scale = pob_softplusf(p) + 0.001f;
+  const float inv = mlp_rcp(scale), ls = pob_logf(scale);
+  const float e = (x - loc) * inv;
+  const float t1 = (((-0.5f * e) * e) - ls) - 0.918938533f;
+  const float ldx = 2.0f * ((0.693147181f - x) - pob_softplusf(-2.0f * x));
+  term = t1 - ldx;
+  u = u > POB_U_MIN ? u : POB_U_MIN;
+  const float eps = 1.41421354f * pob_erfinvf(u);
+  const float y = MLP_FMA(scale, eps, loc);
+  const float ldy = 2.0f * ((0.693147181f - y) - pob_softplusf(-2.0f * y));
+  ent = (1.418938533f + ls) + ldy;
+  dlp_loc = e * inv;
+  dlp_sc = MLP_FMA(e, e, -1.0f) * inv;
+  den_loc = -2.0f * pob_tanhf(y);
+  den_sc = MLP_FMA(eps, den_loc, inv);
+  sig = pob_sigmoidf(p);
+}
+// One row after its components: logp, ent = the sums of the terms (a ascending from +0).  neg_surr
+// = -min(rho adv, clip(rho) adv) and vl = (vs - value)^2 / 4 are the row's parts of the policy and
+// value losses; g_lp = d total / d logp (0 on the clipped branch; a tie takes the unclipped one),
+// dvalue = d total / d value.  No special cases: a NaN compares false and takes the clipped branch.
+POB_MLP_D void pob_ppo_row(const float logp, const float old_logp, const float adv, const float vs, const float value,
+                           const float ppo_epsilon, const float inv_m, float &neg_surr, float &vl, float &g_lp,
+                           float &dvalue) {
+  const float rho = pob_expf(logp - old_logp);
+  const float lo = 1.0f - ppo_epsilon, hi = 1.0f + ppo_epsilon;
+  float c = rho < lo ? lo : rho;
+  c = c > hi ? hi : c;
+  const float s1 = rho * adv, s2 = c * adv;
+  const bool unclipped = s1 <= s2;
+  neg_surr = -(unclipped ? s1 : s2);
+  g_lp = unclipped ? -(s1 * inv_m) : 0.0f;
+  const float verr = vs - value;
+  vl = (verr * verr) * 0.25f;
+  dvalue = (-0.5f * verr) * inv_m;
+}
+// The gradient of one component from the row's g_lp and g_ent = -(entropy_cost inv_m)
+POB_MLP_D void pob_ppo_grad(const float g_lp, const float g_ent, const float dlp_loc, const float dlp_sc,
+                            const float den_loc, const float den_sc, const float sig, float &d_loc, float &d_p) {
+  d_loc = MLP_FMA(g_lp, dlp_loc, g_ent * den_loc);
+  d_p = MLP_FMA(g_lp, dlp_sc, g_ent * den_sc) * sig;
+}
+// losses[4] = total, policy, value, entropy from the float64 sums of neg_surr, vl, ent over M rows
+POB_MLP_D void pob_ppo_finish(const double S_p, const double S_v, const double S_e, const long long M,
+                              const float entropy_cost, float *losses) {
+  const double m = (double)M;
+  const float policy = (float)(S_p / m), value = (float)(S_v / m);
+  const float entropy = (float)(-(double)entropy_cost * (S_e / m));
+  losses[0] = (policy + value) + entropy;
+  losses[1] = policy;
+  losses[2] = value;
+  losses[3] = entropy;
+}
+
 #ifdef POB_MLP_HOST
+// The PPO loss of M minibatch rows: logits (M, 2 A), values (M), u (M, A) the entropy draws
+// (uniform(split(key)[1], (M, A), -1, 1) on the device); raw (N, A), old_logp, advantages, vs (N)
+// in trajectory order, row i reading trajectory row idx[i] (NULL: i).  dlogits (M, 2 A), dvalues
+// (M), partials (n_chunks, 3) may be NULL.  The three sums: rows cut into chunks of POB_PPO_CHUNK,
+// a chunk's triple from +0.0 in ascending row order (partials), the chunk partials added in
+// ascending chunk order from +0.0 (the order of obsnorm_accumulate_ref).
+static inline void ppo_loss_ref(const long long M, const int A, const float *logits, const float *values,
+                                const int32_t *idx, const float *raw, const float *old_logp, const float *advantages,
+                                const float *vs, const float *u, const float entropy_cost, const float ppo_epsilon,
+                                float *dlogits, float *dvalues, float *losses, double *partials) {
+  const float inv_m = 1.0f / (float)M;
+  const float g_ent = -(entropy_cost * inv_m);
+  float f[5 * POB_PPO_MAX_A];
+  double T[3] = {0.0, 0.0, 0.0};
+  for (long long r0 = 0; r0 < M; r0 += POB_PPO_CHUNK) {
+    const long long r1 = r0 + POB_PPO_CHUNK < M ? r0 + POB_PPO_CHUNK : M;
+    double S[3] = {0.0, 0.0, 0.0};
+    for (long long i = r0; i < r1; ++i) {
+      const long long j = idx ? idx[i] : i;
+      float logp = 0.0f, ent = 0.0f;
+      for (int a = 0; a < A; ++a) {
+        float term, en;
+        pob_ppo_component(logits[i * 2 * A + a], logits[i * 2 * A + A + a], raw[j * A + a], u[i * A + a], term, en,
+                          f[5 * a], f[5 * a + 1], f[5 * a + 2], f[5 * a + 3], f[5 * a + 4]);
+        logp = logp + term;
+        ent = ent + en;
+      }
+      float neg_surr, vl, g_lp, dvalue;
+      pob_ppo_row(logp, old_logp[j], advantages[j], vs[j], values[i], ppo_epsilon, inv_m, neg_surr, vl, g_lp, dvalue);
+      if (dvalues) dvalues[i] = dvalue;
+      if (dlogits)
+        for (int a = 0; a < A; ++a)
+          pob_ppo_grad(g_lp, g_ent, f[5 * a], f[5 * a + 1], f[5 * a + 2], f[5 * a + 3], f[5 * a + 4],
+                       dlogits[i * 2 * A + a], dlogits[i * 2 * A + A + a]);
+      S[0] = S[0] + (double)neg_surr;
+      S[1] = S[1] + (double)vl;
+      S[2] = S[2] + (double)ent;
+    }
+    for (int q = 0; q < 3; ++q) {
+      if (partials) partials[(r0 / POB_PPO_CHUNK) * 3 + q] = S[q];
+      T[q] = T[q] + S[q];
+    }
+  }
+  pob_ppo_finish(T[0], T[1], T[2], M, entropy_cost, losses);
+}
+
 // vs, advantages (T, B) of truncation (NULL: zeros), second, reward, values (T, B) row-major and
 // bootstrap (B); either output may be NULL.  Each env on its own, t descending from T - 1.
 static inline void gae_ref(const int T, const long long B, const float *truncation, const float *second,

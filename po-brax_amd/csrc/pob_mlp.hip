@@ -823,3 +823,259 @@ int pob_gae(int T, long long B, const float *truncation, const float *second, in
 }
 
 }  // extern "C"
+
+// ============================================================================ PPO loss
+// ppo_loss_ref of pob_mlp.h (the specification; DESIGN.md "PPO loss").  k_ppo_loss: a block of
+// 256 lanes owns a tile of R consecutive minibatch rows, R = min(256, 1024 / A), so a lane has at
+// most PPO_ITEMS (row, component) items.  The tile's logits arrive in LDS as the contiguous row
+// segment they are in memory (coalesced, all of a lane's loads in flight), pitch 2 A + 1 per row;
+// raw is gathered by idx in whole-row segments.  Consecutive lanes take consecutive components of
+// a row: every item's pob_ppo_component runs once, its five gradient factors stay in the lane's
+// registers, its two terms go back into the logits' own LDS slots.  One lane per row then sums the
+// terms in a ascending (the pitch is odd: conflict-free), finishes pob_ppo_row, stores dvalues and
+// the row's three summands and publishes g_lp; the items form pob_ppo_grad into the same slots,
+// and dlogits leaves as the contiguous segment it is.  k_ppo_chunks: one block per chunk of
+// POB_PPO_CHUNK rows loads the summands coalesced into LDS and three lanes add them in ascending
+// row order (the fixed order admits no tree).  k_ppo_finish: one block stages the chunk partials
+// through LDS, three lanes add them in ascending order, one forms the four scalars.  No atomics,
+// no scratch.
+#define PPO_THREADS 256
+#define PPO_ITEMS 4      // (row, component) items of a lane
+#define PPO_MAX_ROWS 256 // rows of a tile: one row-phase lane each
+#define PPO_ELEMS (PPO_THREADS * PPO_ITEMS)  // a tile holds at most this many components
+#define PPO_FSTAGE 512   // chunk partials k_ppo_finish stages through LDS at a time
+
+// element e of a row-major (rows, W) tile as (row, col), advanced by the block's 256 lanes at a time
+struct ppo_walk {
+  int row, col, dq, dr, W;
+  __device__ __forceinline__ ppo_walk(const int e, const int width) : W(width) {
+    row = e / W; col = e - row * W;
+    dq = PPO_THREADS / W; dr = PPO_THREADS - dq * W;
+  }
+  __device__ __forceinline__ void next() {
+    row += dq; col += dr;
+    if (col >= W) { col -= W; ++row; }
+  }
+};
+
+__global__ __launch_bounds__(PPO_THREADS) void k_ppo_loss(const long long M, const int A, const int R, const float *logits,
+                                                          const float *values, const int32_t *idx, const float *raw,
+                                                          const float *old_logp, const float *advantages, const float *vs,
+                                                          const uint32_t *key, const float entropy_cost,
+                                                          const float ppo_epsilon, const float inv_m, float *dlogits,
+                                                          float *dvalues, float *terms) {
+  __shared__ float L[2 * PPO_ELEMS + PPO_MAX_ROWS];  // (R, 2 A) at pitch 2 A + 1: logits, then terms, then dlogits
+  __shared__ float X[PPO_ELEMS];                     // (R, A): raw
+  __shared__ long long J[PPO_MAX_ROWS];              // the rows' trajectory rows
+  __shared__ float G[PPO_MAX_ROWS];                  // the rows' g_lp
+  const int tid = threadIdx.x, W = 2 * A, P = W + 1;
+  const long long b0 = (long long)blockIdx.x * R;
+  const int valid = M - b0 < R ? (int)(M - b0) : R;
+  // the row phase's operands, loaded ahead of their use
+  float r_old = 0.0f, r_adv = 0.0f, r_vs = 0.0f, r_val = 0.0f;
+  if (tid < valid) {
+    const long long j = idx ? (long long)idx[b0 + tid] : b0 + tid;
+    J[tid] = j;
+    r_old = old_logp[j]; r_adv = advantages[j]; r_vs = vs[j];
+    r_val = values[b0 + tid];
+  }
+  {
+    const float *g = logits + (size_t)b0 * W;
+    const int n = valid * W;
+    ppo_walk w(tid, W);
+    float v[2 * PPO_ITEMS];
+    int at[2 * PPO_ITEMS];
+#pragma unroll
+    for (int k = 0; k < 2 * PPO_ITEMS; ++k) {
+      const int e = tid + PPO_THREADS * k;
+      const bool ok = e < n;
+      v[k] = ok ? g[e] : 0.0f;
+      at[k] = ok ? w.row * P + w.col : -1;
+      w.next();
+    }
+#pragma unroll
+    for (int k = 0; k < 2 * PPO_ITEMS; ++k)
+      if (at[k] >= 0) L[at[k]] = v[k];
+  }
+  __syncthreads();
+  const int n_items = valid * A;
+  {
+    ppo_walk w(tid, A);
+    float v[PPO_ITEMS];
+#pragma unroll
+    for (int k = 0; k < PPO_ITEMS; ++k) {
+      const bool ok = tid + PPO_THREADS * k < n_items;
+      v[k] = ok ? raw[(size_t)J[w.row] * A + w.col] : 0.0f;
+      w.next();
+    }
+#pragma unroll
+    for (int k = 0; k < PPO_ITEMS; ++k)
+      if (tid + PPO_THREADS * k < n_items) X[tid + PPO_THREADS * k] = v[k];
+  }
+  __syncthreads();
+  uint32_t s0, s1;
+  tf_split(key[0], key[1], 2u, 1u, s0, s1);
+  const uint32_t n_draws = (uint32_t)M * (uint32_t)A;
+  float f[PPO_ITEMS][5];
+  {
+    ppo_walk w(tid, A);
+#pragma unroll
+    for (int k = 0; k < PPO_ITEMS; ++k) {
+      const int e = tid + PPO_THREADS * k;
+      if (e < n_items) {
+        const int lo = w.row * P + w.col;
+        const uint32_t i = (uint32_t)(b0 + w.row) * (uint32_t)A + (uint32_t)w.col;
+        const float u = tf_uniform(s0, s1, n_draws, i, -1.0f, 1.0f);
+        float term, ent;
+        pob_ppo_component(L[lo], L[lo + A], X[e], u, term, ent, f[k][0], f[k][1], f[k][2], f[k][3], f[k][4]);
+        L[lo] = term;
+        L[lo + A] = ent;
+      }
+      w.next();
+    }
+  }
+  __syncthreads();
+  if (tid < valid) {
+    float logp = 0.0f, ent = 0.0f;
+    for (int a = 0; a < A; ++a) {
+      logp = logp + L[tid * P + a];
+      ent = ent + L[tid * P + A + a];
+    }
+    float neg_surr, vl, g_lp, dvalue;
+    pob_ppo_row(logp, r_old, r_adv, r_vs, r_val, ppo_epsilon, inv_m, neg_surr, vl, g_lp, dvalue);
+    G[tid] = g_lp;
+    if (dvalues) dvalues[b0 + tid] = dvalue;
+    terms[(size_t)b0 + tid] = neg_surr;
+    terms[(size_t)M + b0 + tid] = vl;
+    terms[2 * (size_t)M + b0 + tid] = ent;
+  }
+  if (!dlogits) return;
+  __syncthreads();
+  {
+    const float g_ent = -(entropy_cost * inv_m);
+    ppo_walk w(tid, A);
+#pragma unroll
+    for (int k = 0; k < PPO_ITEMS; ++k) {
+      if (tid + PPO_THREADS * k < n_items) {
+        const int lo = w.row * P + w.col;
+        float d_loc, d_p;
+        pob_ppo_grad(G[w.row], g_ent, f[k][0], f[k][1], f[k][2], f[k][3], f[k][4], d_loc, d_p);
+        L[lo] = d_loc;
+        L[lo + A] = d_p;
+      }
+      w.next();
+    }
+  }
+  __syncthreads();
+  {
+    float *g = dlogits + (size_t)b0 * W;
+    const int n = valid * W;
+    ppo_walk w(tid, W);
+#pragma unroll
+    for (int k = 0; k < 2 * PPO_ITEMS; ++k) {
+      const int e = tid + PPO_THREADS * k;
+      if (e < n) g[e] = L[w.row * P + w.col];
+      w.next();
+    }
+  }
+}
+
+// partials (n_chunks, 3) <- the float64 sums of the chunk's rows of terms (3, M), rows ascending from +0.0
+__global__ __launch_bounds__(PPO_THREADS) void k_ppo_chunks(const long long M, const float *terms, double *partials) {
+  __shared__ __attribute__((aligned(16))) float T[3][POB_PPO_CHUNK];
+  const int tid = threadIdx.x;
+  const long long r0 = (long long)blockIdx.x * POB_PPO_CHUNK;
+  const int rows = M - r0 < POB_PPO_CHUNK ? (int)(M - r0) : POB_PPO_CHUNK;
+#pragma unroll
+  for (int q = 0; q < 3; ++q)
+#pragma unroll
+    for (int k = 0; k < POB_PPO_CHUNK / PPO_THREADS; ++k) {
+      const int r = tid + PPO_THREADS * k;
+      T[q][r] = r < rows ? terms[(size_t)q * M + r0 + r] : 0.0f;
+    }
+  __syncthreads();
+  if (tid < 3) {
+    double S = 0.0;
+    const float4 *t4 = (const float4 *)T[tid];  // four rows a read; the adds keep the rows' order
+    int r = 0;
+#pragma unroll 4
+    for (; r + 4 <= rows; r += 4) {
+      const float4 v = t4[r >> 2];
+      S = S + (double)v.x;
+      S = S + (double)v.y;
+      S = S + (double)v.z;
+      S = S + (double)v.w;
+    }
+    for (; r < rows; ++r) S = S + (double)T[tid][r];
+    partials[(size_t)blockIdx.x * 3 + tid] = S;
+  }
+}
+
+// losses <- the chunk partials (n_chunks, 3) added per column in ascending chunk order from +0.0:
+// the block stages PPO_FSTAGE chunks at a time through LDS (coalesced), three lanes add them
+__global__ __launch_bounds__(PPO_THREADS) void k_ppo_finish(const long long M, const long long n_chunks,
+                                                            const double *partials, const float entropy_cost,
+                                                            float *losses) {
+  __shared__ double P[3 * PPO_FSTAGE];
+  __shared__ double S[3];
+  const int tid = threadIdx.x;
+  double T = 0.0;
+  for (long long c0 = 0; c0 < n_chunks; c0 += PPO_FSTAGE) {
+    const int n = n_chunks - c0 < PPO_FSTAGE ? (int)(n_chunks - c0) : PPO_FSTAGE;
+    for (int e = tid; e < 3 * n; e += PPO_THREADS) P[e] = partials[(size_t)c0 * 3 + e];
+    __syncthreads();
+    if (tid < 3) {
+#pragma unroll 8
+      for (int c = 0; c < n; ++c) T = T + P[3 * c + tid];
+    }
+    __syncthreads();
+  }
+  if (tid < 3) S[tid] = T;
+  __syncthreads();
+  if (tid == 0) pob_ppo_finish(S[0], S[1], S[2], M, entropy_cost, losses);
+}
+
+static int ppo_chunks(long long M, long long *n_chunks) {
+  if (M < 1) return pob_fail_msg(POB_EINVAL, "ppo_loss: the row count M must be positive");
+  if (M > 0xFFFFFFFELL) return pob_fail_msg(POB_EINVAL, "ppo_loss: too many rows (M A must be below 2^32 - 1)");
+  *n_chunks = (M + POB_PPO_CHUNK - 1) / POB_PPO_CHUNK;
+  return POB_OK;
+}
+
+extern "C" {
+
+int pob_ppo_loss_workspace_bytes(long long M, long long *bytes) {
+  if (!bytes) return pob_fail_msg(POB_EINVAL, "ppo_loss: bytes is NULL");
+  long long n_chunks;
+  const int rc = ppo_chunks(M, &n_chunks);
+  if (rc != POB_OK) return rc;
+  // the chunk partials (n_chunks, 3) float64, then the rows' summands (3, M) float32
+  *bytes = n_chunks * 3 * (long long)sizeof(double) + ((3 * M * (long long)sizeof(float) + 7) & ~7LL);
+  return POB_OK;
+}
+
+int pob_ppo_loss(long long M, int A, const float *logits, const float *values, const int32_t *idx, const float *raw,
+                 const float *old_logp, const float *advantages, const float *vs, const uint32_t *key, float entropy_cost,
+                 float ppo_epsilon, float *dlogits, float *dvalues, float *losses, double *workspace, void *stream) {
+  long long n_chunks;
+  const int rc = ppo_chunks(M, &n_chunks);
+  if (rc != POB_OK) return rc;
+  if (A < 1 || A > POB_PPO_MAX_A) return pob_fail_msg(POB_EINVAL, "ppo_loss: the action size A must be in 1 .. 128");
+  if (M * A >= 4294967295LL) return pob_fail_msg(POB_EINVAL, "ppo_loss: too many action elements (M A must be below 2^32 - 1)");
+  if (!logits || !values || !raw || !old_logp || !advantages || !vs)
+    return pob_fail_msg(POB_EINVAL, "ppo_loss: NULL argument (logits, values, raw, old_logp, advantages, vs)");
+  if (!key) return pob_fail_msg(POB_EINVAL, "ppo_loss: key is NULL");
+  if (!losses || !workspace) return pob_fail_msg(POB_EINVAL, "ppo_loss: NULL argument (losses, workspace)");
+  const int R = PPO_ELEMS / A < PPO_MAX_ROWS ? PPO_ELEMS / A : PPO_MAX_ROWS;
+  const long long tiles = (M + R - 1) / R;
+  hipStream_t st = (hipStream_t)stream;
+  float *terms = (float *)(workspace + n_chunks * 3);
+  const float inv_m = 1.0f / (float)M;
+  hipLaunchKernelGGL(k_ppo_loss, dim3((unsigned)tiles), dim3(PPO_THREADS), 0, st, M, A, R, logits, values, idx, raw, old_logp,
+                     advantages, vs, key, entropy_cost, ppo_epsilon, inv_m, dlogits, dvalues, terms);
+  hipLaunchKernelGGL(k_ppo_chunks, dim3((unsigned)n_chunks), dim3(PPO_THREADS), 0, st, M, (const float *)terms, workspace);
+  hipLaunchKernelGGL(k_ppo_finish, dim3(1), dim3(PPO_THREADS), 0, st, M, n_chunks, (const double *)workspace, entropy_cost, losses);
+  return mlp_hip_check(hipGetLastError(), "k_ppo_loss launch");
+}
+
+}  // extern "C"

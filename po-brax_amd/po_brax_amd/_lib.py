@@ -64,6 +64,7 @@ EXPORTS = (
     "pob_obsnorm_workspace_bytes", "pob_obsnorm_accumulate", "pob_obsnorm_update",
     "pob_mlp_forward_norm", "pob_policy_act_norm", "pob_gru_forward_norm", "pob_gru_policy_act_norm",
     "pob_gae",
+    "pob_ppo_loss_workspace_bytes", "pob_ppo_loss",
 )
 
 
@@ -126,6 +127,11 @@ def _load():
     # T, B, truncation, second, done_input, reward, reward_scale, values, bootstrap, lambda, discount, vs, adv, stream
     lib.pob_gae.argtypes = [C.c_int, C.c_longlong, _VP, _VP, C.c_int, _VP, C.c_float, _VP, _VP, C.c_float, C.c_float,
                             _VP, _VP, _VP]
+    lib.pob_ppo_loss_workspace_bytes.argtypes = [C.c_longlong, C.POINTER(C.c_longlong)]
+    # M, A, logits, values, idx, raw, old_logp, advantages, vs, key, entropy_cost, ppo_epsilon, dlogits, dvalues,
+    # losses, workspace, stream
+    lib.pob_ppo_loss.argtypes = [C.c_longlong, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_float, C.c_float,
+                                 _VP, _VP, _VP, _VP, _VP]
     if lib.pob_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {lib.pob_abi_version()} != {ABI_VERSION}; rebuild it")
     for name in EXPORTS:
