@@ -329,6 +329,26 @@ int pob_ppo_loss(long long M, int A, const float *logits, const float *values, c
                  float *dlogits /* may be NULL */, float *dvalues /* may be NULL */, float *losses /* 4 */,
                  double *workspace, void *stream);
 
+/* ---- MLP backward (ABI v8, additive): the training forward of a pob_mlp, which keeps what the
+ * backward needs, and the backward pass to the parameters and (optionally) the input;
+ * mlp_forward_train_ref / mlp_backward_ref of csrc/pob_mlp.h bit for bit (DESIGN.md "MLP backward":
+ * formulas, summation order).  Layer l is activated when l != n_layers - 1 || activate_final.
+ * forward_train: y (M, sizes[n_layers]) equals pob_mlp_forward's; saved (pob_mlp_saved_bytes) receives
+ * the pre-activation (M, sizes[l + 1]) row-major of every activated layer, ascending l.  backward:
+ * dy (M, sizes[n_layers]) -> dtheta (param_count floats, theta's packing) and dx (M, sizes[0]; may be
+ * NULL).  The workspace is opaque, caller-owned device memory of
+ *   round_up_8(4 M sum_l sizes[l + 1]) + 8 ceil(M / 1024) param_count   bytes
+ * (every layer's delta, then the float64 chunk partials of the parameter gradient): it grows with
+ * ceil(M / 1024) * param_count * 8 bytes, about 0.3 GB for [114 -> 256 x 5 -> 1] at M = 40 960.
+ * M >= 1 and (M + 1024) times the widest layer < 2^31.  Arguments are checked before any HIP call; no
+ * allocation, no atomics, no synchronisation: capturable. */
+int pob_mlp_saved_bytes(const pob_mlp *mlp, long long M, long long *bytes);
+int pob_mlp_forward_train(const pob_mlp *mlp, long long M, const float *x, const float *theta, float *y, float *saved,
+                          void *stream);
+int pob_mlp_backward_workspace_bytes(const pob_mlp *mlp, long long M, long long *bytes);
+int pob_mlp_backward(const pob_mlp *mlp, long long M, const float *x, const float *theta, const float *saved,
+                     const float *dy, float *dtheta, float *dx /* may be NULL */, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

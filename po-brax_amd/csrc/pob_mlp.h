@@ -1,9 +1,10 @@
 // pob_mlp.h -- the scalar math and the plain-C restatement of the policy-network kernels
 // (pob_mlp.hip: k_mlp_forward, k_policy_act, the recurrent k_gru_forward, k_gru_policy_act, the
-// observation normaliser's k_obsnorm_*, k_gae and k_ppo_*).
+// observation normaliser's k_obsnorm_*, k_gae, k_ppo_* and the training forward / backward pass
+// k_mlp_forward_train, k_mlp_bwd_*).
 // Compiled for the device by hipcc and, with POB_MLP_HOST, for the host by g++
-// (tests/host/mlp_host.cpp, gru_host.cpp, obsnorm_host.cpp, gae_host.cpp, ppo_host.cpp); both with
-// -ffp-contract=off.
+// (tests/host/mlp_host.cpp, gru_host.cpp, obsnorm_host.cpp, gae_host.cpp, ppo_host.cpp,
+// mlp_bwd_host.cpp); both with -ffp-contract=off.
 //
 // Every function is a fixed sequence of float32 +, *, fmaf, integer bit operations, and the
 // correctly rounded reciprocal and square root (pob_rcp / pob_sqrt of pob_math.h on the device,
@@ -20,6 +21,7 @@
 #include <stdint.h>
 #ifdef POB_MLP_HOST
 #include <math.h>
+#include <stdlib.h>
 #define POB_MLP_D static inline
 POB_MLP_D float mlp_rcp(float x) { return 1.0f / x; }
 POB_MLP_D float mlp_sqrt(float x) { return sqrtf(x); }
@@ -166,6 +168,19 @@ POB_MLP_D float mlp_activate(const int act, const float x) {
   if (act == POB_ACT_RELU) return x > 0.0f ? x : 0.0f;
   if (act == POB_ACT_SWISH) return pob_swishf(x);
   return pob_tanhf(x);
+}
+
+// The backward pass of the activation: delta = g act'(z) from the saved pre-activation z and the
+// incoming gradient g (DESIGN.md "MLP backward").  relu gives +0 wherever z <= 0 (a NaN z too).
+#define POB_MLP_BWD_CHUNK 1024  // rows of one chunk of the parameter gradient's summation order
+POB_MLP_D float mlp_activate_grad(const int act, const float z, const float g) {
+  if (act == POB_ACT_RELU) return z > 0.0f ? g : 0.0f;
+  if (act == POB_ACT_SWISH) {
+    const float s = pob_sigmoidf(z);
+    return g * MLP_FMA(z * s, 1.0f - s, s);
+  }
+  const float t = pob_tanhf(z);
+  return g * MLP_FMA(-t, t, 1.0f);
 }
 
 // The tanh-normal head of one action component (brax NormalTanhDistribution [ext]): scale =
@@ -439,6 +454,134 @@ static inline void mlp_forward_ref(const int n_layers, const int *sizes, const i
     for (int j = 0; j < sizes[n_layers]; ++j) y[(long long)b * sizes[n_layers] + j] = a[j];
   }
 }
+// ---- the training forward and the backward pass (DESIGN.md "MLP backward"; k_mlp_forward_train,
+// k_mlp_bwd_delta, k_mlp_bwd_weights, k_mlp_bwd_reduce).  Layer l is ACTIVATED when l != n_layers
+// - 1 || activate_final.  saved holds the pre-activation z_l (M, sizes[l + 1]) row-major of every
+// activated layer, the layers one after the other in ascending l.
+static inline bool mlp_layer_activated(const int n_layers, const int activate_final, const int l) {
+  return l != n_layers - 1 || activate_final;
+}
+static inline long long mlp_saved_count(const int n_layers, const int *sizes, const int activate_final, const long long M) {
+  long long n = 0;
+  for (int l = 0; l < n_layers; ++l)
+    if (mlp_layer_activated(n_layers, activate_final, l)) n += M * sizes[l + 1];
+  return n;
+}
+// y = mlp_forward_ref's (the same chain), saved = the pre-activations
+static inline void mlp_forward_train_ref(const int n_layers, const int *sizes, const int activation,
+                                         const int activate_final, const long long M, const float *x, const float *theta,
+                                         float *y, float *saved) {
+  float a[POB_MLP_MAX_WIDTH + 1], o[POB_MLP_MAX_WIDTH + 1];
+  for (long long b = 0; b < M; ++b) {
+    for (int k = 0; k < sizes[0]; ++k) a[k] = x[b * sizes[0] + k];
+    const float *W = theta;
+    float *sv = saved;
+    for (int l = 0; l < n_layers; ++l) {
+      const int in = sizes[l], out = sizes[l + 1];
+      const float *bias = W + (long long)in * out;
+      const bool activate = mlp_layer_activated(n_layers, activate_final, l);
+      for (int j = 0; j < out; ++j) {
+        float acc = bias[j];
+        for (int s = 0; s < mlp_ksteps(in); ++s)
+          for (int h = 0; h < 2; ++h) {
+            const int k = mlp_kfeat(s, h);
+            acc = k < in ? MLP_FMA(W[(long long)k * out + j], a[k], acc) : MLP_FMA(0.0f, 0.0f, acc);
+          }
+        if (activate) sv[b * out + j] = acc;
+        o[j] = activate ? mlp_activate(activation, acc) : acc;
+      }
+      for (int j = 0; j < out; ++j) a[j] = o[j];
+      if (activate) sv += M * out;
+      W = bias + out;
+    }
+    for (int j = 0; j < sizes[n_layers]; ++j) y[b * sizes[n_layers] + j] = a[j];
+  }
+}
+// One element of a parameter gradient: sum over the M rows of a[r] d[r] (a: stride lda, NULL = the
+// constant 1.0f of the bias row; d: stride ldd).  Rows are cut into tiles of 32, a tile's partial
+// is the float32 chain acc = +0, acc = fmaf(a[r], d[r], acc) in ascending r (sixteen k-steps of the
+// 32x32x2 instruction with the row as k, the order of mlp_kfeat); tile partials are added in
+// float64 in ascending order from +0.0 inside chunks of POB_MLP_BWD_CHUNK rows, the chunk partials
+// in float64 in ascending order from +0.0, and the total is rounded to float32 once.  Rows past M
+// add nothing: an accumulator started at +0 is not -0 (but for one corner, below), so the
+// instruction's fmaf(0, 0, acc) of a padded row (or of an odd width's pad in the propagated
+// gradient) changes no bit and is not spelled.  The corner: a product that underflows can round
+// +0 to -0.  Here the float64 addition from +0.0 removes it again; in the propagated gradient of
+// an odd out whose last product so underflows (a delta far below 2^-100) the kernel's pad gives +0
+// where mlp_backward_ref keeps -0.  partials (may be NULL) receives the chunk partials.
+static inline float mlp_bwd_sum(const long long M, const float *a, const long long lda, const float *d, const long long ldd,
+                                double *partials) {
+  double total = 0.0;
+  for (long long c0 = 0; c0 < M; c0 += POB_MLP_BWD_CHUNK) {
+    const long long c1 = c0 + POB_MLP_BWD_CHUNK < M ? c0 + POB_MLP_BWD_CHUNK : M;
+    double chunk = 0.0;
+    for (long long t0 = c0; t0 < c1; t0 += 32) {
+      const long long t1 = t0 + 32 < c1 ? t0 + 32 : c1;
+      float acc = 0.0f;
+      for (long long r = t0; r < t1; ++r) acc = MLP_FMA(a ? a[r * lda] : 1.0f, d[r * ldd], acc);
+      chunk = chunk + (double)acc;
+    }
+    if (partials) partials[c0 / POB_MLP_BWD_CHUNK] = chunk;
+    total = total + chunk;
+  }
+  return (float)total;
+}
+// dtheta (mlp_param_count floats, theta's packing: layer l's block is an (in + 1, out) matrix whose
+// last row is the bias) and dx (M, sizes[0]; may be NULL) from dy (M, sizes[n_layers]), x, theta and
+// the training forward's saved.  l descending from n_layers - 1 with g = dy above the last layer:
+//   delta[r][j] = mlp_activate_grad(z_l[r][j], g[r][j]) if layer l is activated, else g[r][j]
+//   dtheta_l[i][j] = mlp_bwd_sum over r of a[r][i] delta[r][j]; a = layer l's input: x for l = 0,
+//     else mlp_activate(z_{l-1}[r][i]) recomputed (the forward's bits); row i = in: the constant 1
+//   g[r][i] = sum_j W_l[i][j] delta[r][j]: acc = +0, one fmaf(W_l[i][j], delta[r][j], acc) per j in
+//     natural order (the k order of mlp_kfeat over the output features); dx = g of layer 0
+// delta_out (may be NULL) receives every layer's delta (M, sizes[l + 1]), ascending l.  Returns
+// 0, or -1 when its buffers cannot be allocated.
+static inline int mlp_backward_ref(const int n_layers, const int *sizes, const int activation, const int activate_final,
+                                   const long long M, const float *x, const float *theta, const float *saved,
+                                   const float *dy, float *dtheta, float *dx, float *delta_out) {
+  float *delta = (float *)malloc(sizeof(float) * M * POB_MLP_MAX_WIDTH);
+  float *g = (float *)malloc(sizeof(float) * M * POB_MLP_MAX_WIDTH);
+  float *a = (float *)malloc(sizeof(float) * M * POB_MLP_MAX_WIDTH);
+  if (!delta || !g || !a) { free(delta); free(g); free(a); return -1; }
+  long long woff = mlp_param_count(n_layers, sizes), soff = mlp_saved_count(n_layers, sizes, activate_final, M), doff = 0;
+  for (int l = 0; l < n_layers; ++l) doff += M * sizes[l + 1];
+  for (long long e = 0; e < M * sizes[n_layers]; ++e) g[e] = dy[e];
+  for (int l = n_layers - 1; l >= 0; --l) {
+    const int in = sizes[l], out = sizes[l + 1];
+    woff -= ((long long)in + 1) * out;
+    doff -= M * out;
+    const float *W = theta + woff;
+    if (mlp_layer_activated(n_layers, activate_final, l)) {
+      soff -= M * out;
+      for (long long e = 0; e < M * out; ++e) delta[e] = mlp_activate_grad(activation, saved[soff + e], g[e]);
+    } else {
+      for (long long e = 0; e < M * out; ++e) delta[e] = g[e];
+    }
+    if (delta_out)
+      for (long long e = 0; e < M * out; ++e) delta_out[doff + e] = delta[e];
+    if (l == 0) {
+      for (long long e = 0; e < M * in; ++e) a[e] = x[e];
+    } else {  // z_{l-1} lies right below z_l in saved
+      const float *zp = saved + (soff - M * in);
+      for (long long e = 0; e < M * in; ++e) a[e] = mlp_activate(activation, zp[e]);
+    }
+    for (int i = 0; i <= in; ++i)
+      for (int j = 0; j < out; ++j)
+        dtheta[woff + (long long)i * out + j] = mlp_bwd_sum(M, i < in ? a + i : NULL, in, delta + j, out, NULL);
+    if (l > 0 || dx) {
+      float *dst = l > 0 ? g : dx;
+      for (long long r = 0; r < M; ++r)
+        for (int i = 0; i < in; ++i) {
+          float acc = 0.0f;
+          for (int j = 0; j < out; ++j) acc = MLP_FMA(W[(long long)i * out + j], delta[r * out + j], acc);
+          dst[r * in + i] = acc;
+        }
+    }
+  }
+  free(delta); free(g); free(a);
+  return 0;
+}
+
 // The actor on rows of logits (B, 2 A) and the uniform draws u (B, A); logp sums the terms in
 // natural order a = 0 .. A - 1 from +0.  Deterministic: action = tanh(loc), raw = loc, logp
 // is not written.

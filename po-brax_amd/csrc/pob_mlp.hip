@@ -4,6 +4,7 @@
 //   k_mlp_forward   y = MLP(x): every layer in one launch
 //   k_policy_act    the same forward, then the tanh-normal head (brax NormalTanhDistribution [ext])
 //   k_gru_forward, k_gru_policy_act   the recurrent actor (pre-MLP, GRU cell, post-MLP; below)
+//   k_mlp_forward_train, k_mlp_bwd_*  the training forward and the backward pass (at the end)
 //
 // One 64-lane block (one wave) owns a tile of 32 batch rows.  It computes Y^T = W^T X^T with
 // v_mfma_f32_32x32x2_f32: the env is the C column (lane & 31), the A operand of k-step s is row
@@ -387,13 +388,16 @@ static int image_rows(const MlpDesc &d, bool head, int &split) {
 }
 
 // the normalising instantiation only where a table is given: the plain one is the code it was
-#define MLP_DISPATCH_N(KERNEL, N, cls, ...)                                                    \
-  switch (cls) {                                                                               \
-    case 0: hipLaunchKernelGGL((KERNEL<64, N>), grid, dim3(64), 0, st, __VA_ARGS__); break;    \
-    case 1: hipLaunchKernelGGL((KERNEL<152, N>), grid, dim3(64), 0, st, __VA_ARGS__); break;   \
-    case 2: hipLaunchKernelGGL((KERNEL<288, N>), grid, dim3(64), 0, st, __VA_ARGS__); break;   \
-    default: hipLaunchKernelGGL((KERNEL<512, N>), grid, dim3(64), 0, st, __VA_ARGS__); break;  \
+// (TAIL: the template arguments after the pool height, each written MLP_TARG(x); may be empty)
+#define MLP_TARG(x) , x
+#define MLP_DISPATCH_T(KERNEL, TAIL, cls, ...)                                                    \
+  switch (cls) {                                                                                  \
+    case 0: hipLaunchKernelGGL((KERNEL<64 TAIL>), grid, dim3(64), 0, st, __VA_ARGS__); break;     \
+    case 1: hipLaunchKernelGGL((KERNEL<152 TAIL>), grid, dim3(64), 0, st, __VA_ARGS__); break;    \
+    case 2: hipLaunchKernelGGL((KERNEL<288 TAIL>), grid, dim3(64), 0, st, __VA_ARGS__); break;    \
+    default: hipLaunchKernelGGL((KERNEL<512 TAIL>), grid, dim3(64), 0, st, __VA_ARGS__); break;   \
   }
+#define MLP_DISPATCH_N(KERNEL, N, cls, ...) MLP_DISPATCH_T(KERNEL, MLP_TARG(N), cls, __VA_ARGS__)
 #define MLP_DISPATCH(KERNEL, cls, ...)                                \
   if (norm) { MLP_DISPATCH_N(KERNEL, true, cls, __VA_ARGS__, norm, norm_clip) } \
   else { MLP_DISPATCH_N(KERNEL, false, cls, __VA_ARGS__, norm, norm_clip) }
@@ -1076,6 +1080,299 @@ int pob_ppo_loss(long long M, int A, const float *logits, const float *values, c
   hipLaunchKernelGGL(k_ppo_chunks, dim3((unsigned)n_chunks), dim3(PPO_THREADS), 0, st, M, (const float *)terms, workspace);
   hipLaunchKernelGGL(k_ppo_finish, dim3(1), dim3(PPO_THREADS), 0, st, M, n_chunks, (const double *)workspace, entropy_cost, losses);
   return mlp_hip_check(hipGetLastError(), "k_ppo_loss launch");
+}
+
+}  // extern "C"
+
+// ============================================================================ MLP backward
+// mlp_forward_train_ref / mlp_backward_ref of pob_mlp.h (the specification; DESIGN.md "MLP
+// backward").  k_mlp_forward_train: k_mlp_forward with every activated layer's accumulator tile
+// also stored to `saved` before the activation, through the LDS image (coalesced); the activation
+// is then applied to the image in place.  k_mlp_bwd_delta: one wave per tile of 32 rows walks the
+// layers downwards with the incoming gradient in one LDS image [feature][env] and delta in the
+// other: z_l is staged like an observation tile, delta_l = mlp_activate_grad(z_l, g) is stored to
+// the workspace (M, out) coalesced, and G^T = W_l Delta^T runs on the MFMA with accumulators from
+// +0 (the A operand of k-step s is W_l[i][2 s + h], a column walk of the L2-resident row-major
+// matrix); the last G is dx.  k_mlp_bwd_weights: one wave per (chunk of POB_MLP_BWD_CHUNK rows,
+// 32 x 32 tile of a layer's (in + 1, out) block): per tile of 32 rows sixteen MFMAs with the row
+// as k (A = the layer's input, mlp_activate(z_{l-1}) recomputed on load, 1 for the bias row; B =
+// delta; both row-contiguous across lanes), the sixteen float32 accumulators then added into
+// sixteen float64 registers and zeroed; the float64 chunk partial goes to the workspace.
+// k_mlp_bwd_reduce: one lane per parameter adds the chunk partials in ascending order and rounds
+// once.  Vector stores only, no atomics, no scratch, no allocation.
+POB_MLP_D bool mlp_activated(const MlpDesc &d, const int l) { return l != d.n_layers - 1 || d.act_final; }
+
+// element e of an image's first 32 * width floats as its place in the image
+POB_MLP_D int mlp_img_at(const int e) { return (e >> 5) * MLP_PITCH + (e & 31); }
+
+template <int H>
+__global__ __launch_bounds__(64) void k_mlp_forward_train(const MlpDesc d, const int split, const int B, const float *x,
+                                                          const float *theta, float *y, float *saved) {
+  __shared__ float img[H * MLP_PITCH];
+  const int lane = threadIdx.x, b0 = blockIdx.x * MLP_ROWS;
+  const int valid = B - b0 < MLP_ROWS ? B - b0 : MLP_ROWS;
+  float *src = img, *dst = img + split * MLP_PITCH;
+  mlp_tile_load<false>(src, x, d.sizes[0], b0, valid, nullptr, nullptr, nullptr, 0.0f, lane);
+  __syncthreads();
+  const float *W = theta;
+  float *sv = saved;
+  for (int l = 0; l < d.n_layers; ++l) {
+    const int in = d.sizes[l], out = d.sizes[l + 1];
+    const float *bias = W + (size_t)in * out;
+    mlp_layer(src, dst, W, bias, in, out, false, d.act, lane);
+    __syncthreads();
+    if (mlp_activated(d, l)) {
+      mlp_tile_store(sv, dst, 0, out, b0, valid, lane);
+      sv += (size_t)B * out;
+      __syncthreads();
+      for (int e = lane; e < MLP_ROWS * out; e += 64) dst[mlp_img_at(e)] = mlp_activate(d.act, dst[mlp_img_at(e)]);
+      __syncthreads();
+    }
+    W = bias + out;
+    float *t = src; src = dst; dst = t;
+  }
+  mlp_tile_store(y, src, 0, d.sizes[d.n_layers], b0, valid, lane);
+}
+
+// dst image (in features) <- W (in, out) row-major times the src image (out features): per
+// element acc = +0 and one fmaf(W[i][k], src[k], acc) per k in the order of mlp_kfeat
+POB_MLP_D void mlp_layer_back(const float *src, float *dst, const float *W, const int in, const int out, const int lane) {
+  const int j = lane & 31, h = lane >> 5;
+  const int ks = mlp_ksteps(out);
+  for (int it = 0; it < in; it += 32) {
+    const int row = it + j;
+    const bool rok = row < in;
+    mlp_f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    for (int s0 = 0; s0 < ks; s0 += MLP_KUNROLL) {
+      float a[MLP_KUNROLL], b[MLP_KUNROLL];
+#pragma unroll
+      for (int u = 0; u < MLP_KUNROLL; ++u) {
+        const int k = mlp_kfeat(s0 + u, h);
+        const bool kok = k < out;
+        a[u] = (kok && rok) ? W[(size_t)row * out + k] : 0.0f;
+        b[u] = kok ? src[k * MLP_PITCH + j] : 0.0f;
+      }
+#pragma unroll
+      for (int u = 0; u < MLP_KUNROLL; ++u)
+        if (s0 + u < ks) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b[u], acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int i = it + mlp_acc_row(r, h);
+      if (i < in) dst[i * MLP_PITCH + j] = acc[r];
+    }
+  }
+}
+
+template <int H>
+__global__ __launch_bounds__(64) void k_mlp_bwd_delta(const MlpDesc d, const int split, const int B, const float *theta,
+                                                      const float *saved, const float *dy, float *delta, float *dx) {
+  __shared__ float img[H * MLP_PITCH];
+  const int lane = threadIdx.x, b0 = blockIdx.x * MLP_ROWS;
+  const int valid = B - b0 < MLP_ROWS ? B - b0 : MLP_ROWS;
+  float *cur = img, *oth = img + split * MLP_PITCH;  // cur holds the incoming gradient
+  size_t woff = 0, soff = 0, doff = 0;
+  for (int l = 0; l < d.n_layers; ++l) {
+    woff += ((size_t)d.sizes[l] + 1) * d.sizes[l + 1];
+    doff += (size_t)B * d.sizes[l + 1];
+    if (mlp_activated(d, l)) soff += (size_t)B * d.sizes[l + 1];
+  }
+  mlp_tile_load<false>(cur, dy, d.sizes[d.n_layers], b0, valid, nullptr, nullptr, nullptr, 0.0f, lane);
+  __syncthreads();
+  for (int l = d.n_layers - 1; l >= 0; --l) {
+    const int in = d.sizes[l], out = d.sizes[l + 1];
+    woff -= ((size_t)in + 1) * out;
+    doff -= (size_t)B * out;
+    float *D = cur, *G = oth;
+    if (mlp_activated(d, l)) {
+      soff -= (size_t)B * out;
+      mlp_tile_load<false>(oth, saved + soff, out, b0, valid, nullptr, nullptr, nullptr, 0.0f, lane);
+      __syncthreads();
+      for (int e = lane; e < MLP_ROWS * out; e += 64)
+        oth[mlp_img_at(e)] = mlp_activate_grad(d.act, oth[mlp_img_at(e)], cur[mlp_img_at(e)]);
+      __syncthreads();
+      D = oth; G = cur;
+    }
+    mlp_tile_store(delta + doff, D, 0, out, b0, valid, lane);
+    if (l == 0 && !dx) break;
+    mlp_layer_back(D, G, theta + woff, in, out, lane);
+    __syncthreads();
+    cur = G; oth = D;
+  }
+  if (dx) mlp_tile_store(dx, cur, 0, d.sizes[0], b0, valid, lane);
+}
+
+__global__ __launch_bounds__(64) void k_mlp_bwd_weights(const MlpDesc d, const int B, const long long n_params,
+                                                        const float *x, const float *saved, const float *delta,
+                                                        double *partials) {
+  const int lane = threadIdx.x, j = lane & 31, h = lane >> 5;
+  // blockIdx.y counts the 32 x 32 tiles of the layers' (in + 1, out) blocks, layer by layer
+  int t = blockIdx.y, l = 0, tj;
+  size_t woff = 0, aoff = 0, doff = 0;  // layer l's block of theta, z_{l-1} in saved, delta_l
+  for (;; ++l) {
+    const int in = d.sizes[l], out = d.sizes[l + 1];
+    tj = (out + 31) >> 5;
+    const int n = ((in + 32) >> 5) * tj;
+    if (t < n || l == d.n_layers - 1) break;
+    t -= n;
+    woff += ((size_t)in + 1) * out;
+    doff += (size_t)B * out;
+    if (l > 0) aoff += (size_t)B * in;
+  }
+  const int in = d.sizes[l], out = d.sizes[l + 1];
+  const int ai = (t / tj) * 32 + j, bj = (t % tj) * 32 + j;
+  const bool a_ok = ai < in, a_one = ai == in, b_ok = bj < out;
+  const float *A = l ? saved + aoff : x, *D = delta + doff;
+  const int r_begin = blockIdx.x * POB_MLP_BWD_CHUNK;
+  const int r_end = B - r_begin < POB_MLP_BWD_CHUNK ? B : r_begin + POB_MLP_BWD_CHUNK;
+  double sum[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) sum[r] = 0.0;
+  for (int rt = r_begin; rt < r_end; rt += 32) {
+    float a[16], b[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int row = rt + mlp_kfeat(u, h);
+      const bool rok = row < r_end;
+      a[u] = (rok && a_ok) ? A[(size_t)row * in + ai] : 0.0f;
+      b[u] = (rok && b_ok) ? D[(size_t)row * out + bj] : 0.0f;
+    }
+    if (l) {
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const float v = mlp_activate(d.act, a[u]);
+        a[u] = (rt + mlp_kfeat(u, h) < r_end && a_ok) ? v : 0.0f;
+      }
+    }
+    if (a_one) {
+#pragma unroll
+      for (int u = 0; u < 16; ++u) a[u] = rt + mlp_kfeat(u, h) < r_end ? 1.0f : 0.0f;
+    }
+    mlp_f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+#pragma unroll
+    for (int u = 0; u < 16; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b[u], acc, 0, 0, 0);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sum[r] = sum[r] + (double)acc[r];
+  }
+  double *P = partials + (size_t)blockIdx.x * (size_t)n_params + woff;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int i = (t / tj) * 32 + mlp_acc_row(r, h);
+    if (i <= in && b_ok) P[(size_t)i * out + bj] = sum[r];
+  }
+}
+
+__global__ __launch_bounds__(256) void k_mlp_bwd_reduce(const double *partials, const long long n_chunks,
+                                                        const long long n_params, float *dtheta) {
+  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= n_params) return;
+  double T = 0.0;
+  for (long long c0 = 0; c0 < n_chunks; c0 += OBSNORM_RSTAGE) {
+    double v[OBSNORM_RSTAGE];
+#pragma unroll
+    for (int u = 0; u < OBSNORM_RSTAGE; ++u) v[u] = c0 + u < n_chunks ? partials[(size_t)(c0 + u) * n_params + p] : 0.0;
+#pragma unroll
+    for (int u = 0; u < OBSNORM_RSTAGE; ++u)
+      if (c0 + u < n_chunks) T = T + v[u];
+  }
+  dtheta[p] = (float)T;
+}
+
+static int mlp_widest(const MlpDesc &d) {
+  int w = 1;
+  for (int l = 0; l <= d.n_layers; ++l)
+    if (d.sizes[l] > w) w = d.sizes[l];
+  return w;
+}
+
+// the pool of the delta kernel, two images of the widest layer: the height class of MLP_DISPATCH_T
+static int train_rows(const MlpDesc &d, int &split) {
+  split = mlp_widest(d);
+  const int rows = 2 * split;
+  return rows <= 64 ? 0 : (rows <= 152 ? 1 : (rows <= 288 ? 2 : 3));
+}
+
+// the float counts of saved and of the workspace's delta arrays.  (M + a chunk) times the widest
+// layer must stay below 2^31: the kernels count rows, and a chunk's end, in int
+static int mlp_bwd_counts(const pob_mlp *m, long long M, long long *n_saved, long long *n_delta) {
+  if (!m) return pob_fail_msg(POB_EINVAL, "mlp is NULL");
+  if (M < 1) return pob_fail_msg(POB_EINVAL, "mlp: the row count M must be positive");
+  if (M + POB_MLP_BWD_CHUNK >= (1LL << 31) / mlp_widest(m->d))
+    return pob_fail_msg(POB_EINVAL, "mlp: too many rows ((M + 1024) times the widest layer must be below 2^31)");
+  *n_saved = *n_delta = 0;
+  for (int l = 0; l < m->d.n_layers; ++l) {
+    *n_delta += M * m->d.sizes[l + 1];
+    if (l != m->d.n_layers - 1 || m->d.act_final) *n_saved += M * m->d.sizes[l + 1];
+  }
+  return POB_OK;
+}
+
+extern "C" {
+
+int pob_mlp_saved_bytes(const pob_mlp *m, long long M, long long *bytes) {
+  if (!bytes) return pob_fail_msg(POB_EINVAL, "mlp: bytes is NULL");
+  long long n_saved, n_delta;
+  const int rc = mlp_bwd_counts(m, M, &n_saved, &n_delta);
+  if (rc != POB_OK) return rc;
+  *bytes = n_saved * (long long)sizeof(float);
+  return POB_OK;
+}
+
+int pob_mlp_forward_train(const pob_mlp *m, long long M, const float *x, const float *theta, float *y, float *saved,
+                          void *stream) {
+  long long n_saved, n_delta;
+  const int rc = mlp_bwd_counts(m, M, &n_saved, &n_delta);
+  if (rc != POB_OK) return rc;
+  if (!x || !theta || !y || (n_saved && !saved)) return pob_fail_msg(POB_EINVAL, "mlp: NULL argument (x, theta, y, saved)");
+  int split;
+  const int cls = image_rows(m->d, false, split);
+  const int B = (int)M;
+  const dim3 grid((unsigned)((B + MLP_ROWS - 1) / MLP_ROWS));
+  hipStream_t st = (hipStream_t)stream;
+  MLP_DISPATCH_T(k_mlp_forward_train, , cls, m->d, split, B, x, theta, y, saved)
+  return mlp_hip_check(hipGetLastError(), "k_mlp_forward_train launch");
+}
+
+int pob_mlp_backward_workspace_bytes(const pob_mlp *m, long long M, long long *bytes) {
+  if (!bytes) return pob_fail_msg(POB_EINVAL, "mlp: bytes is NULL");
+  long long n_saved, n_delta;
+  const int rc = mlp_bwd_counts(m, M, &n_saved, &n_delta);
+  if (rc != POB_OK) return rc;
+  const long long n_chunks = (M + POB_MLP_BWD_CHUNK - 1) / POB_MLP_BWD_CHUNK;
+  // the delta arrays (M, sizes[l + 1]) float32 of every layer, then the chunk partials (n_chunks, n_params) float64
+  *bytes = ((n_delta * (long long)sizeof(float) + 7) & ~7LL) + n_chunks * m->n_params * (long long)sizeof(double);
+  return POB_OK;
+}
+
+int pob_mlp_backward(const pob_mlp *m, long long M, const float *x, const float *theta, const float *saved,
+                     const float *dy, float *dtheta, float *dx, void *workspace, void *stream) {
+  long long n_saved, n_delta;
+  const int rc = mlp_bwd_counts(m, M, &n_saved, &n_delta);
+  if (rc != POB_OK) return rc;
+  if (!x || !theta || !dy || !dtheta || !workspace || (n_saved && !saved))
+    return pob_fail_msg(POB_EINVAL, "mlp: NULL argument (x, theta, saved, dy, dtheta, workspace)");
+  const int B = (int)M;
+  const long long n_chunks = (M + POB_MLP_BWD_CHUNK - 1) / POB_MLP_BWD_CHUNK;
+  float *delta = (float *)workspace;
+  double *partials = (double *)((char *)workspace + ((n_delta * (long long)sizeof(float) + 7) & ~7LL));
+  hipStream_t st = (hipStream_t)stream;
+  {
+    int split;
+    const int cls = train_rows(m->d, split);
+    const dim3 grid((unsigned)((B + MLP_ROWS - 1) / MLP_ROWS));
+    MLP_DISPATCH_T(k_mlp_bwd_delta, , cls, m->d, split, B, theta, saved, dy, delta, dx)
+  }
+  unsigned tiles = 0;
+  for (int l = 0; l < m->d.n_layers; ++l) tiles += (unsigned)(((m->d.sizes[l] + 32) >> 5) * ((m->d.sizes[l + 1] + 31) >> 5));
+  hipLaunchKernelGGL(k_mlp_bwd_weights, dim3((unsigned)n_chunks, tiles), dim3(64), 0, st, m->d, B, m->n_params, x, saved,
+                     (const float *)delta, partials);
+  hipLaunchKernelGGL(k_mlp_bwd_reduce, dim3((unsigned)((m->n_params + 255) / 256)), dim3(256), 0, st,
+                     (const double *)partials, n_chunks, m->n_params, dtheta);
+  return mlp_hip_check(hipGetLastError(), "k_mlp_bwd launch");
 }
 
 }  // extern "C"

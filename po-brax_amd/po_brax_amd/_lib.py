@@ -65,6 +65,7 @@ EXPORTS = (
     "pob_mlp_forward_norm", "pob_policy_act_norm", "pob_gru_forward_norm", "pob_gru_policy_act_norm",
     "pob_gae",
     "pob_ppo_loss_workspace_bytes", "pob_ppo_loss",
+    "pob_mlp_saved_bytes", "pob_mlp_forward_train", "pob_mlp_backward_workspace_bytes", "pob_mlp_backward",
 )
 
 
@@ -132,6 +133,12 @@ def _load():
     # losses, workspace, stream
     lib.pob_ppo_loss.argtypes = [C.c_longlong, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_float, C.c_float,
                                  _VP, _VP, _VP, _VP, _VP]
+    lib.pob_mlp_saved_bytes.argtypes = [_VP, C.c_longlong, C.POINTER(C.c_longlong)]
+    lib.pob_mlp_backward_workspace_bytes.argtypes = [_VP, C.c_longlong, C.POINTER(C.c_longlong)]
+    # mlp, M, x, theta, y, saved, stream
+    lib.pob_mlp_forward_train.argtypes = [_VP, C.c_longlong, _VP, _VP, _VP, _VP, _VP]
+    # mlp, M, x, theta, saved, dy, dtheta, dx, workspace, stream
+    lib.pob_mlp_backward.argtypes = [_VP, C.c_longlong, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]
     if lib.pob_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {lib.pob_abi_version()} != {ABI_VERSION}; rebuild it")
     for name in EXPORTS:

@@ -6,6 +6,8 @@ flax ``Dense.kernel``'s layout), of which the ``{"hidden_i": {"kernel", "bias"}}
 views.  ``apply`` runs the fused HIP kernel (``pob_mlp_forward``: every layer in one launch on
 the f32 matrix cores) when ``x`` is a CUDA float32 tensor and no gradient is required, and the
 same network in plain torch ops otherwise (autograd for the learner, and the CPU).
+``model.apply_native`` is ``apply`` whose backward pass runs in the engine too
+(``pob_mlp_forward_train`` / ``pob_mlp_backward``: DESIGN.md "MLP backward").
 ``NormalTanhPolicy`` is the actor: forward + brax's tanh-normal head in one launch
 (``pob_policy_act``), capture-safe, so it drops into ``rollout.PolicyRollout`` and is what
 ``rollout.ActorRollout`` unrolls.  Formulas, layouts and what is pinned: DESIGN.md "Policy
@@ -145,6 +147,7 @@ class FeedForwardModel:
     layer_sizes: Optional[Tuple[int, ...]] = None  # (obs_size, *layer_sizes)
     activation: Optional[int] = None               # 0 relu, 1 swish, 2 tanh
     mlp: Optional[MLPHandle] = None
+    apply_native: Any = None                       # apply whose backward pass is the engine's too
 
 
 def _forward_torch(sizes, act: int, theta_or_params, x: torch.Tensor) -> torch.Tensor:
@@ -214,7 +217,61 @@ def make_model(layer_sizes: Sequence[int], obs_size: int, activation: Any = "swi
                                       _lib.stream_handle(x.device)))
         return y.reshape(*x.shape[:-1], sizes[-1])
 
-    return FeedForwardModel(init=init, apply=apply, layer_sizes=sizes, activation=act, mlp=mlp)
+    class _NativeMLP(torch.autograd.Function):
+        """theta (contiguous float32 CUDA), x2 (M, sizes[0]) contiguous float32 CUDA, M >= 1."""
+
+        @staticmethod
+        def forward(ctx, theta, x2):
+            M, dev = int(x2.shape[0]), x2.device
+            need = C.c_longlong()
+            check(lib.pob_mlp_saved_bytes(mlp.handle, M, C.byref(need)))
+            saved = torch.empty(need.value // 4, dtype=torch.float32, device=dev)
+            y = torch.empty((M, sizes[-1]), dtype=torch.float32, device=dev)
+            check(lib.pob_mlp_forward_train(mlp.handle, M, ptr(x2), ptr(theta), ptr(y), ptr(saved),
+                                            _lib.stream_handle(dev)))
+            ctx.save_for_backward(theta, x2, saved)
+            return y
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable  # the kernels are invisible to autograd: no double backward
+        def backward(ctx, dy):
+            theta, x2, saved = ctx.saved_tensors
+            M, dev = int(x2.shape[0]), x2.device
+            dy = dy.contiguous()
+            need = C.c_longlong()
+            check(lib.pob_mlp_backward_workspace_bytes(mlp.handle, M, C.byref(need)))
+            workspace = torch.empty(need.value // 8, dtype=torch.float64, device=dev)
+            dtheta = torch.empty_like(theta)
+            dx = torch.empty_like(x2) if ctx.needs_input_grad[1] else None
+            check(lib.pob_mlp_backward(mlp.handle, M, ptr(x2), ptr(theta), ptr(saved), ptr(dy), ptr(dtheta), ptr(dx),
+                                       ptr(workspace), _lib.stream_handle(dev)))
+            return (dtheta if ctx.needs_input_grad[0] else None), dx
+
+    def apply_native(params, x: torch.Tensor) -> torch.Tensor:
+        """``apply`` whose backward pass runs in the engine as well: for a ``Params`` (or a namespace
+        with ``.theta``) whose ``theta`` is a contiguous float32 CUDA tensor and a float32 CUDA ``x``,
+        the forward is ``pob_mlp_forward_train`` (``apply``'s fused bits, the pre-activations kept)
+        and the backward ``pob_mlp_backward`` (``theta.grad``, and ``x.grad`` only when ``x`` requires
+        it).  Anything else (the CPU, other dtypes, the dict-of-views form) takes the torch ops under
+        autograd; when no gradient is needed this is ``apply``."""
+        theta = getattr(params, "theta", None)
+        need_grad = torch.is_grad_enabled() and (x.requires_grad or (
+            theta.requires_grad if theta is not None else any(t.requires_grad for p in params.values() for t in p.values())))
+        if not need_grad:
+            return apply(params, x)
+        native = (theta is not None and x.is_cuda and x.dtype == torch.float32 and theta.is_cuda
+                  and theta.dtype == torch.float32 and theta.is_contiguous() and x.numel() > 0)
+        if not native:
+            return _forward_torch(sizes, act, params, x)
+        if theta.numel() != mlp.param_count:
+            raise ValueError(f"theta has {theta.numel()} elements, the network {mlp.param_count}")
+        if x.shape[-1] != sizes[0]:
+            raise ValueError(f"x must be (..., {sizes[0]})")
+        y = _NativeMLP.apply(theta, x.reshape(-1, sizes[0]).contiguous())
+        return y.reshape(*x.shape[:-1], sizes[-1])
+
+    return FeedForwardModel(init=init, apply=apply, layer_sizes=sizes, activation=act, mlp=mlp,
+                            apply_native=apply_native)
 
 
 def make_models(policy_params_size: int, obs_size: int) -> Tuple[FeedForwardModel, FeedForwardModel]:
