@@ -118,6 +118,8 @@ def _declare(_lib):
         _lib.orc_get_mesh_variant.restype = C.c_int
         _lib.orc_contact_stats_enable.argtypes = [C.c_int]
         _lib.orc_mesh_contacts.argtypes = [_FP, _FP, _FP, C.c_int, C.c_float, _FP]
+        _lib.orc_contacts_record.argtypes = [C.POINTER(C.c_int), C.c_int]
+        _lib.orc_walls.argtypes = [C.c_void_p, _FP]
     return _lib
 
 
@@ -220,6 +222,22 @@ class OracleEnv:
         ci, co = self._cstate(s), self._cstate(out)
         self._L.orc_step(self.h, B, C.byref(ci), _p(act), C.byref(co), flags, episode_length, nthreads)
         return out
+
+    def walls(self) -> np.ndarray:
+        """The arena's wall boxes, rows (cx, cy, cos, sin, hx, hy)."""
+        out = np.zeros((8, 6), np.float32)
+        return out[:self._L.orc_walls(self.h, _p(out))].copy()
+
+    def step_recorded(self, s, act: np.ndarray, nsub: int = 5, **kw):
+        """step() with the contact record on (single-threaded): the new state and the wall
+        contacts per env, collide substep and dynamic body, int64 (B, nsub, 9)."""
+        buf = np.zeros((np.asarray(act).shape[0], nsub, 9), np.int32)
+        self._L.orc_contacts_record(buf.ctypes.data_as(C.POINTER(C.c_int)), nsub)
+        try:
+            out = self.step(s, act, nthreads=1, **kw)
+        finally:
+            self._L.orc_contacts_record(None, 0)
+        return out, buf.astype(np.int64)
 
     def gym_autoreset(self, s, gym_key: np.ndarray, nthreads: int = 1):
         cs = self._cstate(s)

@@ -1253,6 +1253,23 @@ static int face_items(const orc_env *e, int i, int w, v3 pa, v3 pb) {
 }
 #endif
 
+/* Test hook (every build; single-threaded; no effect on any result): while set, detect() writes
+ * the wall contacts (ground contacts excluded) of each dynamic body per env and collide substep
+ * of orc_step into buf[(env * nsub + substep) * 9 + body] (tests/wall_arrange.py).  NULL
+ * switches it off. */
+static int *g_ctr_buf = NULL;
+static int g_ctr_nsub = 0, g_ctr_env = 0, g_ctr_sub = 0;
+void orc_contacts_record(int *buf, int nsub) { g_ctr_buf = buf; g_ctr_nsub = nsub; }
+/* the arena's wall boxes: out (cx, cy, cos, sin, hx, hy) x the returned count (at most 8) */
+int orc_walls(const orc_env *e, float *out) {
+  for (int w = 0; w < e->n_walls; ++w) {
+    float *o = out + 6 * w;
+    o[0] = e->wall_c[w].x; o[1] = e->wall_c[w].y; o[2] = e->wall_cos[w]; o[3] = e->wall_sin[w];
+    o[4] = e->wall_h[w].x; o[5] = e->wall_h[w].y;
+  }
+  return e->n_walls;
+}
+
 /* contact detection for the collide substep: ground (CapsulePlane on the torso and the four
  * lower legs), then per capsule its Ant x Arena contacts (wall_contact 0: every penetrating
  * triangle of every wall; 1: the deepest sphere-box contact over end points x walls). */
@@ -1272,6 +1289,7 @@ static void detect(const orc_env *e, const body_t *b, contacts_t *ct) {
   if (g_flop_mode == 1) kernel_wall_masks(e, b, lane_mask);
 #endif
   if (e->n_walls > 0) CST(7, 1);
+  int *const ctr = g_ctr_buf && g_ctr_sub < g_ctr_nsub ? g_ctr_buf + ((size_t)g_ctr_env * g_ctr_nsub + g_ctr_sub++) * NDYN : NULL;
 #ifdef ORC_COUNT_FLOPS
   if (g_flop_mode == 1 && g_items_buf && g_items_sub < g_items_nsub) {
     v3 sa[NDYN], sb[NDYN];
@@ -1307,6 +1325,7 @@ static void detect(const orc_env *e, const body_t *b, contacts_t *ct) {
 #endif
       }
       const int nh = ct->count - before;
+      if (ctr) ctr[i] = nh;
       if (e->n_walls > 0) {
         CST(3, nh > 0);
         if (g_cst_on && nh > g_cst[4]) g_cst[4] = nh;
@@ -1326,6 +1345,7 @@ static void detect(const orc_env *e, const body_t *b, contacts_t *ct) {
 #endif
         if (pen > best) { best = pen; bn = n; btau = q == 0 ? 1.0f : -1.0f; }
       }
+    if (ctr) ctr[i] = best > 0.0f;
     if (best > 0.0f) {
       const int m = ct->count++;
       ct->pen[m] = best; ct->n[m] = bn; ct->tau[m] = btau; ct->e[m] = V(0, 0, 0);
@@ -1888,6 +1908,7 @@ static void step_one(const orc_env *e, int b, const orc_state *in, const float *
 #ifdef ORC_COUNT_FLOPS
   g_items_env = b; g_items_sub = 0;
 #endif
+  if (g_ctr_buf) { g_ctr_env = b; g_ctr_sub = 0; }
   const float x_before = bd.x[0].x;
   v3 cv[NDYN], ca[NDYN];
   physics_step(e, &bd, act + (size_t)b * NJ, cv, ca);

@@ -88,6 +88,12 @@ int orc_flops_set_mode(int mode);
  * [8..15] histogram of wall contacts per capsule per detection (0..6, >= 7) */
 void orc_contact_stats(long long out[16]);
 void orc_contact_stats_enable(int on);
+/* test hook (single-threaded runs only): while buf is set, every orc_step writes the wall contacts
+ * (ground contacts excluded) of each dynamic body per env and collide substep into
+ * buf[(env * nsub + substep) * 9 + body]; NULL switches it off.  No effect on any result. */
+void orc_contacts_record(int *buf, int nsub);
+/* the arena's wall boxes: out (cx, cy, cos, sin, hx, hy) x the returned count (at most 8) */
+int orc_walls(const orc_env *e, float *out);
 /* test hook: mesh contacts of one capsule (world end points a, b; seg 0 = sphere at a, radius r)
  * against one wall box (cx, cy, cz, cos, sin, hx, hy, hz): out (tau, nx, ny, nz, pen, cd) x count */
 int orc_mesh_contacts(const float *wall, const float *a, const float *b, int seg, float r, float *out);
