@@ -349,6 +349,34 @@ int pob_mlp_backward_workspace_bytes(const pob_mlp *mlp, long long M, long long 
 int pob_mlp_backward(const pob_mlp *mlp, long long M, const float *x, const float *theta, const float *saved,
                      const float *dy, float *dtheta, float *dx /* may be NULL */, void *workspace, void *stream);
 
+/* ---- Recurrent backward (ABI v8, additive): the training forward of a pob_gru over a window of T
+ * steps and its truncated backward pass through time; gru_sequence_forward_train_ref /
+ * gru_sequence_backward_ref of csrc/pob_mlp.h bit for bit (DESIGN.md "Recurrent backward": formulas,
+ * operation and summation order).  obs (T, B, D) and reset (T, B; may be NULL) are trajectory arrays
+ * read in place: sequence m is env idx[m] (int32, every entry in [0, B): not checked), or env m
+ * without idx (then M == B); h0 (B, H) is read through idx too.  reset[t][b] != 0 (a NaN too, -0.0
+ * not): env b starts step t from h = +0, and no gradient crosses that step's entry.  norm: the
+ * (3, D) normaliser table of pob_gru_forward_norm, or NULL.
+ * forward_train: y (T, M, out) and h_last (M, H; may be NULL) equal T chained pob_gru_forward_norm
+ * calls on the gathered rows; saved (pob_gru_sequence_saved_bytes) is opaque.  backward: dy (T, M, out)
+ * and dh_last (M, H; NULL: zeros) -> dtheta (param_count floats, theta's packing) and dh0 (M, H; may
+ * be NULL).  idx and reset must be the forward's.  There is no gradient to the observations.  The
+ * workspace is opaque, caller-owned device memory (pob_gru_sequence_backward_workspace_bytes: every
+ * delta array, then 8 ceil(T M / 1024) param_count bytes of float64 chunk partials).  T >= 1, M >= 1,
+ * and (T M + 1024) times the widest array (4 H included) < 2^31.  Arguments are checked before any
+ * HIP call; no allocation, no atomics, no synchronisation: forward and backward capture into one graph. */
+int pob_gru_sequence_saved_bytes(const pob_gru *g, int T, long long M, long long *bytes);
+int pob_gru_sequence_forward_train(const pob_gru *g, int T, long long M, long long B, const float *obs,
+                                   const int32_t *idx /* may be NULL */, const float *h0,
+                                   const float *reset /* may be NULL */, const float *theta, float *y,
+                                   float *h_last /* may be NULL */, float *saved, const float *norm /* may be NULL */,
+                                   float norm_clip, void *stream);
+int pob_gru_sequence_backward_workspace_bytes(const pob_gru *g, int T, long long M, long long *bytes);
+int pob_gru_sequence_backward(const pob_gru *g, int T, long long M, long long B, const int32_t *idx /* may be NULL */,
+                              const float *reset /* may be NULL */, const float *theta, const float *saved,
+                              const float *dy, const float *dh_last /* may be NULL */, float *dtheta,
+                              float *dh0 /* may be NULL */, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,10 +1,11 @@
 // pob_mlp.h -- the scalar math and the plain-C restatement of the policy-network kernels
 // (pob_mlp.hip: k_mlp_forward, k_policy_act, the recurrent k_gru_forward, k_gru_policy_act, the
 // observation normaliser's k_obsnorm_*, k_gae, k_ppo_* and the training forward / backward pass
-// k_mlp_forward_train, k_mlp_bwd_*).
+// k_mlp_forward_train, k_mlp_bwd_*, and the recurrent window's k_gru_seq_forward, k_gru_seq_backward,
+// k_gru_bwd_weights).
 // Compiled for the device by hipcc and, with POB_MLP_HOST, for the host by g++
 // (tests/host/mlp_host.cpp, gru_host.cpp, obsnorm_host.cpp, gae_host.cpp, ppo_host.cpp,
-// mlp_bwd_host.cpp); both with -ffp-contract=off.
+// mlp_bwd_host.cpp, gru_bwd_host.cpp); both with -ffp-contract=off.
 //
 // Every function is a fixed sequence of float32 +, *, fmaf, integer bit operations, and the
 // correctly rounded reciprocal and square root (pob_rcp / pob_sqrt of pob_math.h on the device,
@@ -706,5 +707,228 @@ static inline void gru_policy_ref(const int n_pre, const int *pre_sizes, const i
                                   float *logp, float *raw) {
   gru_forward_ref(n_pre, pre_sizes, H, n_post, post_sizes, activation, B, obs, theta, reset, h_in, logits, h_out, h_in_copy);
   policy_head_ref(B, post_sizes[n_post - 1] >> 1, logits, u, deterministic, action, logp, raw);
+}
+#endif
+
+// ---------------------------------------------------------------------------- recurrent backward
+// The training forward of the recurrent network over a window of T steps and its truncated
+// backward pass through time (DESIGN.md "Recurrent backward"; k_gru_seq_forward,
+// k_gru_seq_backward, k_gru_bwd_weights).  R = T M rows in the flat order r = t M + m.  What the
+// forward keeps, as float offsets into `saved`, every array (R, width) row-major:
+//   xin   the normalised observation rows (R, D), only under a pre-MLP
+//   pre   the pre-MLP's pre-activations, mlp_forward_train_ref's layout (every layer activated)
+//   xc    the cell's input x (R, I): the pre-MLP's output, or the normalised observation
+//   hin   the h each step started from, after the reset (R, H)
+//   gate  r, z, ch, n (R, 4 H): four runs of H per row
+//   hn    h' (R, H)
+//   post  the post-MLP's pre-activations (its last layer is not activated)
+// and the backward's delta arrays, as float offsets into its workspace: the pre-MLP's layers
+// (R, pre[l + 1]) ascending, the cell's (R, 4 H) = delta_r, delta_z, delta_xn, delta_hn, the
+// post-MLP's layers (R, post[l]) ascending; `n_delta` floats in all, the float64 chunk partials
+// (n_chunks, n_params) behind them at the next multiple of 8 bytes.
+struct gru_seq_plan {
+  long long xin, pre, xc, hin, gate, hn, post, n_saved;
+  long long d_pre, d_cell, d_post, n_delta;
+};
+static inline gru_seq_plan gru_seq_layout(const int n_pre, const int *pre, const int H, const int n_post, const int *post,
+                                          const long long R) {
+  gru_seq_plan p;
+  const long long D = pre[0], I = pre[n_pre];
+  long long o = 0, e = 0;
+  p.xin = o; if (n_pre) o += R * D;
+  p.pre = o; p.d_pre = e;
+  for (int l = 0; l < n_pre; ++l) { o += R * pre[l + 1]; e += R * pre[l + 1]; }
+  p.xc = o; o += R * I;
+  p.hin = o; o += R * H;
+  p.gate = o; o += R * 4 * H;
+  p.hn = o; o += R * H;
+  p.post = o; p.d_cell = e; e += R * 4 * H;
+  p.d_post = e;
+  for (int l = 0; l < n_post; ++l) { if (l != n_post - 1) o += R * post[l]; e += R * post[l]; }
+  p.n_saved = o; p.n_delta = e;
+  return p;
+}
+// The element-wise part of the cell's backward pass for one feature: g = the gradient arriving at
+// h', hin the h the step started from.  One rounding per spelled operation; r, z, n are the
+// forward's values, never another spelling of sigmoid or tanh.
+POB_MLP_D void pob_gru_cell_grad(const float g, const float hin, const float r, const float z, const float ch, const float n,
+                                 float &d_r, float &d_z, float &d_xn, float &d_hn) {
+  const float omz = 1.0f - z;
+  const float dz = g * (hin - n);
+  const float dn = g * omz;
+  const float ds = dn * MLP_FMA(-n, n, 1.0f);
+  d_xn = ds;
+  d_hn = ds * r;
+  d_r = ((ds * ch) * r) * (1.0f - r);
+  d_z = (dz * z) * omz;
+}
+
+#ifdef POB_MLP_HOST
+// y (T, M, out), h_last (M, H; may be NULL) and saved (gru_seq_layout's n_saved floats) of the
+// window: obs (T, B, D) and reset (T, B; may be NULL) are read in place, sequence m being env
+// idx[m] (NULL: m, M == B); h0 (B, H); norm (3, D) may be NULL.  Step t is gru_forward_ref on the
+// gathered, normalised rows from the h' of step t - 1 (h0 at t = 0): the same chains.
+static inline void gru_sequence_forward_train_ref(const int n_pre, const int *pre_sizes, const int H, const int n_post,
+                                                  const int *post_sizes, const int activation, const int T, const long long M,
+                                                  const long long B, const float *obs, const int32_t *idx, const float *h0,
+                                                  const float *reset, const float *norm, const float norm_clip,
+                                                  const float *theta, float *y, float *h_last, float *saved) {
+  float a[POB_MLP_MAX_WIDTH + 1], o[POB_MLP_MAX_WIDTH + 1], c[POB_MLP_MAX_WIDTH + 1];
+  float r[POB_GRU_MAX_HIDDEN], z[POB_GRU_MAX_HIDDEN], cx[POB_GRU_MAX_HIDDEN], ch[POB_GRU_MAX_HIDDEN], hn[POB_GRU_MAX_HIDDEN];
+  float h[POB_GRU_MAX_HIDDEN];
+  const int D = pre_sizes[0], I = pre_sizes[n_pre], out_w = post_sizes[n_post - 1];
+  const long long R = (long long)T * M;
+  const gru_seq_plan p = gru_seq_layout(n_pre, pre_sizes, H, n_post, post_sizes, R);
+  for (long long m = 0; m < M; ++m) {
+    const long long b = idx ? idx[m] : m;
+    for (int k = 0; k < H; ++k) h[k] = h0[b * H + k];
+    for (int t = 0; t < T; ++t) {
+      const long long row = (long long)t * M + m;
+      for (int k = 0; k < D; ++k) {
+        const float v = obs[((long long)t * B + b) * D + k];
+        a[k] = norm ? pob_obsnorm_apply(v, norm[k], norm[D + k], norm_clip) : v;
+        if (n_pre) saved[p.xin + row * D + k] = a[k];
+      }
+      const float *W = theta;
+      long long so = p.pre;
+      for (int l = 0; l < n_pre; ++l) {
+        const int in = pre_sizes[l], out = pre_sizes[l + 1];
+        const float *bias = W + (long long)in * out;
+        for (int j = 0; j < out; ++j) {
+          const float acc = mlp_chain_ref(bias[j], W, out, j, a, in);
+          saved[so + row * out + j] = acc;
+          o[j] = mlp_activate(activation, acc);
+        }
+        for (int j = 0; j < out; ++j) a[j] = o[j];
+        so += R * out;
+        W = bias + out;
+      }
+      const bool zero = reset && reset[(long long)t * B + b] != 0.0f;
+      for (int k = 0; k < I; ++k) { c[k] = a[k]; saved[p.xc + row * I + k] = a[k]; }
+      for (int k = 0; k < H; ++k) { c[I + k] = zero ? 0.0f : h[k]; saved[p.hin + row * H + k] = c[I + k]; }
+      gru_cell_ref(I, H, c, W, r, z, cx, ch, hn);
+      W += 3LL * H * I + 3LL * H * H + 4 * H;
+      for (int k = 0; k < H; ++k) {
+        float *gt = saved + p.gate + row * 4 * H;
+        gt[k] = r[k]; gt[H + k] = z[k]; gt[2 * H + k] = ch[k];
+        // n is not among gru_cell_ref's outputs: the same expression, hence the same bits
+        gt[3 * H + k] = pob_tanhf(MLP_FMA(r[k], ch[k], cx[k]));
+        saved[p.hn + row * H + k] = hn[k];
+        h[k] = hn[k]; a[k] = hn[k];
+      }
+      int in = H;
+      so = p.post;
+      for (int l = 0; l < n_post; ++l) {
+        const int out = post_sizes[l];
+        const float *bias = W + (long long)in * out;
+        for (int j = 0; j < out; ++j) {
+          const float acc = mlp_chain_ref(bias[j], W, out, j, a, in);
+          if (l != n_post - 1) saved[so + row * out + j] = acc;
+          o[j] = l != n_post - 1 ? mlp_activate(activation, acc) : acc;
+        }
+        for (int j = 0; j < out; ++j) a[j] = o[j];
+        if (l != n_post - 1) so += R * out;
+        W = bias + out;
+        in = out;
+      }
+      for (int j = 0; j < out_w; ++j) y[row * out_w + j] = a[j];
+    }
+    if (h_last)
+      for (int k = 0; k < H; ++k) h_last[m * H + k] = h[k];
+  }
+}
+
+// dtheta (gru_param_count floats, theta's packing: every block an (in + 1, out) matrix whose last
+// row is the bias) and dh0 (M, H; may be NULL) from dy (T, M, out), dh_last (M, H; NULL: zeros),
+// theta and the forward's saved.  reset (T, B; may be NULL) and idx as in the forward.
+//   post-MLP: mlp_backward_ref over the R rows (input hn, activate_final = 0); its dx = g_post
+//   cell, t descending, carry[m] = dh_last[m] (or +0) before t = T - 1:
+//     g_h = g_post[r] + carry;  pob_gru_cell_grad(g_h, hin, r, z, ch, n) -> the row's four deltas
+//     acc = +0; acc = fmaf(W_rz[I + i][j], delta_rz[j], acc) for j = 0 .. 2 H - 1 (delta_rz =
+//       [delta_r ; delta_z]), then acc = fmaf(W_hn[i][j], delta_hn[j], acc) for j = 0 .. H - 1;
+//       carry[i] = fmaf(g_h[i], z[i], acc), or +0 where reset[t][b] != 0 (a NaN too)
+//     g_x[k] (under a pre-MLP): acc = +0, the same chain over W_rz[k][.] and delta_rz, then over
+//       W_xn[k][.] and delta_xn
+//   cell blocks of dtheta: mlp_bwd_sum over the R rows of ([xc ; hin], delta_rz), (xc, delta_xn),
+//     (hin, delta_hn), the bias rows with the constant 1
+//   pre-MLP: mlp_backward_ref over the R rows (input xin, activate_final = 1, dy = g_x, no dx)
+//   dh0 = the carry after t = 0
+// delta_out (may be NULL) receives the workspace's delta arrays (gru_seq_layout's n_delta floats).
+// Returns 0, or -1 when its buffers cannot be allocated.
+static inline int gru_sequence_backward_ref(const int n_pre, const int *pre_sizes, const int H, const int n_post,
+                                            const int *post_sizes, const int activation, const int T, const long long M,
+                                            const long long B, const int32_t *idx, const float *reset, const float *theta,
+                                            const float *saved, const float *dy, const float *dh_last, float *dtheta,
+                                            float *dh0, float *delta_out) {
+  const int I = pre_sizes[n_pre];
+  const long long R = (long long)T * M;
+  const gru_seq_plan p = gru_seq_layout(n_pre, pre_sizes, H, n_post, post_sizes, R);
+  float *delta = (float *)malloc(sizeof(float) * (p.n_delta + 1));
+  float *g_post = (float *)malloc(sizeof(float) * R * H);
+  float *g_x = (float *)malloc(sizeof(float) * (R * I + 1));
+  float *carry = (float *)malloc(sizeof(float) * M * H);
+  if (!delta || !g_post || !g_x || !carry) { free(delta); free(g_post); free(g_x); free(carry); return -1; }
+  long long w_cell = 0;
+  for (int l = 0; l < n_pre; ++l) w_cell += ((long long)pre_sizes[l] + 1) * pre_sizes[l + 1];
+  const long long w_post = w_cell + 3LL * H * I + 3LL * H * H + 4 * H;
+  int rc = 0;
+  {
+    int sizes[POB_GRU_MAX_POST + 1];
+    sizes[0] = H;
+    for (int l = 0; l < n_post; ++l) sizes[l + 1] = post_sizes[l];
+    rc = mlp_backward_ref(n_post, sizes, activation, 0, R, saved + p.hn, theta + w_post, saved + p.post, dy, dtheta + w_post,
+                          g_post, delta + p.d_post);
+  }
+  const float *W_rz = theta + w_cell, *W_xn = W_rz + (long long)(I + H) * 2 * H + 2 * H;
+  const float *W_hn = W_xn + (long long)I * H + H;
+  float *dc = delta + p.d_cell;
+  for (long long e = 0; e < M * H; ++e) carry[e] = dh_last ? dh_last[e] : 0.0f;
+  for (int t = T - 1; t >= 0 && !rc; --t)
+    for (long long m = 0; m < M; ++m) {
+      const long long row = (long long)t * M + m, b = idx ? idx[m] : m;
+      const float *gt = saved + p.gate + row * 4 * H, *hin = saved + p.hin + row * H;
+      float *d = dc + row * 4 * H, g_h[POB_GRU_MAX_HIDDEN];
+      for (int j = 0; j < H; ++j) {
+        g_h[j] = g_post[row * H + j] + carry[m * H + j];
+        pob_gru_cell_grad(g_h[j], hin[j], gt[j], gt[H + j], gt[2 * H + j], gt[3 * H + j], d[j], d[H + j], d[2 * H + j],
+                          d[3 * H + j]);
+      }
+      const bool zero = reset && reset[(long long)t * B + b] != 0.0f;
+      for (int i = 0; i < H; ++i) {
+        float acc = 0.0f;
+        for (int j = 0; j < 2 * H; ++j) acc = MLP_FMA(W_rz[(long long)(I + i) * 2 * H + j], d[j], acc);
+        for (int j = 0; j < H; ++j) acc = MLP_FMA(W_hn[(long long)i * H + j], d[3 * H + j], acc);
+        carry[m * H + i] = zero ? 0.0f : MLP_FMA(g_h[i], gt[H + i], acc);
+      }
+      if (n_pre)
+        for (int k = 0; k < I; ++k) {
+          float acc = 0.0f;
+          for (int j = 0; j < 2 * H; ++j) acc = MLP_FMA(W_rz[(long long)k * 2 * H + j], d[j], acc);
+          for (int j = 0; j < H; ++j) acc = MLP_FMA(W_xn[(long long)k * H + j], d[2 * H + j], acc);
+          g_x[row * I + k] = acc;
+        }
+    }
+  if (!rc) {
+    const float *xc = saved + p.xc, *hin = saved + p.hin;
+    float *d_rz = dtheta + w_cell, *d_xn = d_rz + (long long)(I + H + 1) * 2 * H, *d_hn = d_xn + (long long)(I + 1) * H;
+    for (int i = 0; i <= I + H; ++i)
+      for (int j = 0; j < 2 * H; ++j) {
+        const float *a = i < I ? xc + i : (i < I + H ? hin + (i - I) : NULL);
+        d_rz[(long long)i * 2 * H + j] = mlp_bwd_sum(R, a, i < I ? I : H, dc + j, 4 * H, NULL);
+      }
+    for (int i = 0; i <= I; ++i)
+      for (int j = 0; j < H; ++j) d_xn[(long long)i * H + j] = mlp_bwd_sum(R, i < I ? xc + i : NULL, I, dc + 2 * H + j, 4 * H, NULL);
+    for (int i = 0; i <= H; ++i)
+      for (int j = 0; j < H; ++j) d_hn[(long long)i * H + j] = mlp_bwd_sum(R, i < H ? hin + i : NULL, H, dc + 3 * H + j, 4 * H, NULL);
+    if (n_pre)
+      rc = mlp_backward_ref(n_pre, pre_sizes, activation, 1, R, saved + p.xin, theta, saved + p.pre, g_x, dtheta, NULL,
+                            delta + p.d_pre);
+    if (dh0)
+      for (long long e = 0; e < M * H; ++e) dh0[e] = carry[e];
+    if (delta_out)
+      for (long long e = 0; e < p.n_delta; ++e) delta_out[e] = delta[e];
+  }
+  free(delta); free(g_post); free(g_x); free(carry);
+  return rc;
 }
 #endif

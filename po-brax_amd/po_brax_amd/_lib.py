@@ -66,6 +66,8 @@ EXPORTS = (
     "pob_gae",
     "pob_ppo_loss_workspace_bytes", "pob_ppo_loss",
     "pob_mlp_saved_bytes", "pob_mlp_forward_train", "pob_mlp_backward_workspace_bytes", "pob_mlp_backward",
+    "pob_gru_sequence_saved_bytes", "pob_gru_sequence_forward_train", "pob_gru_sequence_backward_workspace_bytes",
+    "pob_gru_sequence_backward",
 )
 
 
@@ -139,6 +141,14 @@ def _load():
     lib.pob_mlp_forward_train.argtypes = [_VP, C.c_longlong, _VP, _VP, _VP, _VP, _VP]
     # mlp, M, x, theta, saved, dy, dtheta, dx, workspace, stream
     lib.pob_mlp_backward.argtypes = [_VP, C.c_longlong, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]
+    lib.pob_gru_sequence_saved_bytes.argtypes = [_VP, C.c_int, C.c_longlong, C.POINTER(C.c_longlong)]
+    lib.pob_gru_sequence_backward_workspace_bytes.argtypes = [_VP, C.c_int, C.c_longlong, C.POINTER(C.c_longlong)]
+    # gru, T, M, B, obs, idx, h0, reset, theta, y, h_last, saved, norm, norm_clip, stream
+    lib.pob_gru_sequence_forward_train.argtypes = [_VP, C.c_int, C.c_longlong, C.c_longlong, _VP, _VP, _VP, _VP, _VP, _VP,
+                                                   _VP, _VP, _VP, C.c_float, _VP]
+    # gru, T, M, B, idx, reset, theta, saved, dy, dh_last, dtheta, dh0, workspace, stream
+    lib.pob_gru_sequence_backward.argtypes = [_VP, C.c_int, C.c_longlong, C.c_longlong, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                              _VP, _VP, _VP]
     if lib.pob_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {lib.pob_abi_version()} != {ABI_VERSION}; rebuild it")
     for name in EXPORTS:

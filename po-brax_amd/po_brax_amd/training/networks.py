@@ -16,6 +16,9 @@ networks".
 ``make_recurrent_model`` / ``RecurrentTanhPolicy`` are the recurrent counterparts (pre-MLP ->
 GRU cell -> post-MLP, ``pob_gru_forward`` / ``pob_gru_policy_act``, the hidden state carried on
 the device), unrolled by ``rollout.RecurrentActorRollout``: DESIGN.md "Recurrent actor".
+``model.apply_sequence`` runs a window of T steps in torch ops and ``model.apply_sequence_native`` in
+the engine, forward and truncated-BPTT backward (``pob_gru_sequence_forward_train`` /
+``pob_gru_sequence_backward``): DESIGN.md "Recurrent backward".
 
 Both policies take ``normalizer=`` (``normalization.ObservationNormalizer``): the running
 observation normaliser applied inside the actor kernel's tile load (``pob_*_policy_act_norm``):
@@ -359,6 +362,8 @@ class RecurrentModel:
     post_sizes: Optional[Tuple[int, ...]] = None
     activation: Optional[int] = None
     gru: Optional[GRUHandle] = None
+    apply_sequence: Any = None          # a window of T steps in torch ops (autograd, any dtype and device)
+    apply_sequence_native: Any = None   # the same window in the engine, forward and backward
 
 
 def _recurrent_torch(pre, H, post, act, theta, x, h, reset):
@@ -448,8 +453,136 @@ def make_recurrent_model(pre_sizes: Sequence[int], hidden_size: int, post_sizes:
                                       None, _lib.stream_handle(x.device)))
         return y, h_new
 
+    def _check_theta(theta):
+        if theta.numel() != gru.param_count:
+            raise ValueError(f"theta has {theta.numel()} elements, the network {gru.param_count}")
+
+    def apply_sequence(params, x: torch.Tensor, h0: torch.Tensor, reset: Optional[torch.Tensor] = None):
+        """A window of T steps in torch ops: x (T, M, obs_size), h0 (M, hidden_size), reset (T, M)
+        (non-zero: sequence m starts step t from h = 0) -> ``(y (T, M, post_sizes[-1]), h_last)``.
+        Any dtype and device; differentiable by autograd in ``theta``, ``x`` and ``h0``."""
+        theta = params.theta
+        _check_theta(theta)
+        if x.dim() != 3 or x.shape[2] != pre[0] or x.shape[0] < 1:
+            raise ValueError(f"x must be (T, M, {pre[0]}) with T >= 1")
+        T, M = int(x.shape[0]), int(x.shape[1])
+        if tuple(h0.shape) != (M, H):
+            raise ValueError(f"h0 must be ({M}, {H})")
+        if reset is not None and tuple(reset.shape) != (T, M):
+            raise ValueError(f"reset must be ({T}, {M})")
+        h, ys = h0, []
+        for t in range(T):
+            y, h = _recurrent_torch(pre, H, post, act, theta, x[t], h, None if reset is None else reset[t])
+            ys.append(y)
+        return torch.stack(ys), h
+
+    class _NativeSequence(torch.autograd.Function):
+        """theta, obs (T, B, D), h0 (B, H) contiguous float32 CUDA; reset (T, B) float32 or None;
+        idx (M,) int32 or None; table (3, D) or None."""
+
+        @staticmethod
+        def forward(ctx, theta, obs, h0, reset, idx, table, clip):
+            T, B, dev = int(obs.shape[0]), int(obs.shape[1]), obs.device
+            M = B if idx is None else int(idx.shape[0])
+            need = C.c_longlong()
+            check(lib.pob_gru_sequence_saved_bytes(gru.handle, T, M, C.byref(need)))
+            saved = torch.empty(need.value // 4, dtype=torch.float32, device=dev)
+            y = torch.empty((T, M, post[-1]), dtype=torch.float32, device=dev)
+            h_last = torch.empty((M, H), dtype=torch.float32, device=dev)
+            check(lib.pob_gru_sequence_forward_train(gru.handle, T, M, B, ptr(obs), ptr(idx), ptr(h0), ptr(reset), ptr(theta),
+                                                     ptr(y), ptr(h_last), ptr(saved), ptr(table), float(clip),
+                                                     _lib.stream_handle(dev)))
+            ctx.save_for_backward(theta, saved, reset, idx)
+            ctx.dims = (T, M, B)
+            return y, h_last
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable  # the kernels are invisible to autograd: no double backward
+        def backward(ctx, dy, dh_last):
+            theta, saved, reset, idx = ctx.saved_tensors
+            T, M, B = ctx.dims
+            dev = theta.device
+            need = C.c_longlong()
+            check(lib.pob_gru_sequence_backward_workspace_bytes(gru.handle, T, M, C.byref(need)))
+            workspace = torch.empty(need.value // 8, dtype=torch.float64, device=dev)
+            dtheta = torch.empty_like(theta)
+            dh0_m = torch.empty((M, H), dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
+            dy = dy.contiguous()
+            dh_last = None if dh_last is None else dh_last.contiguous()
+            check(lib.pob_gru_sequence_backward(gru.handle, T, M, B, ptr(idx), ptr(reset), ptr(theta), ptr(saved), ptr(dy),
+                                                ptr(dh_last), ptr(dtheta), ptr(dh0_m), ptr(workspace),
+                                                _lib.stream_handle(dev)))
+            dh0 = dh0_m
+            if dh0_m is not None and idx is not None:  # h0 is (B, H): the sequences' rows, zeros elsewhere
+                dh0 = torch.zeros((B, H), dtype=torch.float32, device=dev).index_add_(0, idx.long(), dh0_m)
+            return (dtheta if ctx.needs_input_grad[0] else None), None, dh0, None, None, None, None
+
+    def apply_sequence_native(params, obs: torch.Tensor, h0: torch.Tensor, reset: Optional[torch.Tensor] = None,
+                              idx: Optional[torch.Tensor] = None, normalizer=None):
+        """``apply_sequence`` over trajectory arrays read in place, forward and backward in the engine
+        (``pob_gru_sequence_forward_train`` / ``pob_gru_sequence_backward``: DESIGN.md "Recurrent
+        backward"): obs (T, B, obs_size), h0 (B, hidden_size), reset (T, B); sequence m is env
+        ``idx[m]`` (int32 (M,); None: every env, M = B); ``normalizer`` (an ``ObservationNormalizer``)
+        is applied to the observation rows -> ``(y (T, M, out), h_last (M, hidden_size))``.  Contiguous
+        float32 CUDA tensors take the kernels when a gradient is needed: ``theta.grad`` always,
+        ``h0.grad`` only when ``h0`` requires it, never a gradient to ``obs``; differentiable once.
+        Anything else (the CPU, other dtypes, no gradient needed) is ``apply_sequence`` on the
+        gathered, normalised rows."""
+        theta = getattr(params, "theta", None)
+        for name, t in (("params.theta", theta), ("obs", obs), ("h0", h0)):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{name} must be a torch.Tensor")
+            if not t.is_floating_point():
+                raise TypeError(f"{name} must be a floating-point tensor, got {t.dtype}")
+        _check_theta(theta)
+        if obs.dim() != 3 or obs.shape[2] != pre[0] or obs.shape[0] < 1 or obs.shape[1] < 1:
+            raise ValueError(f"obs must be (T, B, {pre[0]}) with T >= 1 and B >= 1")
+        T, B = int(obs.shape[0]), int(obs.shape[1])
+        if tuple(h0.shape) != (B, H):
+            raise ValueError(f"h0 must be ({B}, {H})")
+        if h0.dtype != obs.dtype or h0.device != obs.device:
+            raise TypeError(f"h0 is {h0.dtype} on {h0.device}, obs {obs.dtype} on {obs.device}")
+        if theta.dtype != obs.dtype or theta.device != obs.device:
+            raise TypeError(f"params.theta is {theta.dtype} on {theta.device}, obs {obs.dtype} on {obs.device}")
+        if reset is not None:
+            if not isinstance(reset, torch.Tensor):
+                raise TypeError("reset must be a torch.Tensor")
+            if tuple(reset.shape) != (T, B):
+                raise ValueError(f"reset must be ({T}, {B})")
+            if reset.device != obs.device:
+                raise TypeError(f"reset is on {reset.device}, obs on {obs.device}")
+        if idx is not None:
+            if not (isinstance(idx, torch.Tensor) and idx.dtype == torch.int32 and idx.dim() == 1 and idx.shape[0] >= 1):
+                raise ValueError("idx must be an int32 tensor (M,) with M >= 1")
+            if idx.device != obs.device:
+                raise TypeError(f"idx is on {idx.device}, obs on {obs.device}")
+        if normalizer is not None and not callable(getattr(normalizer, "apply", None)):
+            raise TypeError("normalizer must be a normalization.ObservationNormalizer (or have its apply)")
+        table = getattr(normalizer, "table", None)  # the kernels read the table; anything else only has apply
+        if table is not None and tuple(table.shape) != (3, pre[0]):
+            raise ValueError(f"normalizer.table must be (3, {pre[0]}), got {tuple(table.shape)}")
+        need_grad = torch.is_grad_enabled() and (theta.requires_grad or h0.requires_grad)
+        native = (need_grad and not obs.requires_grad
+                  and all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in (theta, obs, h0))
+                  and (idx is None or idx.is_contiguous())
+                  and (normalizer is None or (table is not None and table.is_cuda and table.dtype == torch.float32
+                                              and table.is_contiguous())))
+        if native:
+            rs = None if reset is None else reset.detach().to(torch.float32).contiguous()
+            return _NativeSequence.apply(theta, obs.detach(), h0, rs, idx, table,
+                                         0.0 if normalizer is None else normalizer.clip)
+        x, h, rs = obs, h0, reset
+        if idx is not None:
+            j = idx.long()
+            x, h = obs.index_select(1, j), h0.index_select(0, j)
+            rs = None if reset is None else reset.index_select(1, j)
+        if normalizer is not None:
+            x = normalizer.apply(x.reshape(-1, pre[0])).reshape(x.shape)
+        return apply_sequence(params, x, h, rs)
+
     return RecurrentModel(init=init, apply=apply, initial_state=initial_state, pre_sizes=pre, hidden_size=H,
-                          post_sizes=post, activation=act, gru=gru)
+                          post_sizes=post, activation=act, gru=gru, apply_sequence=apply_sequence,
+                          apply_sequence_native=apply_sequence_native)
 
 
 class RecurrentTanhPolicy:
