@@ -120,6 +120,8 @@ def _declare(_lib):
         _lib.orc_mesh_contacts.argtypes = [_FP, _FP, _FP, C.c_int, C.c_float, _FP]
         _lib.orc_contacts_record.argtypes = [C.POINTER(C.c_int), C.c_int]
         _lib.orc_walls.argtypes = [C.c_void_p, _FP]
+        _lib.orc_physics_only.argtypes = [C.c_void_p, _FP, _FP, _FP, _FP, _FP, _FP, _FP]
+        _lib.orc_joint_angle_vel.argtypes = [C.c_void_p, _FP, _FP, _FP, _FP, _FP, _FP]
     return _lib
 
 
@@ -252,6 +254,29 @@ class OracleEnv:
         self._L.orc_default_qp(self.h, _p(qpos), _p(qvel), *[_p(o) for o in out])
         return out
 
+    def contact_info(self, pos, rot, vel, ang):
+        """sys.info(qp).contact of one env's static state: (vel, ang), each (N, 3)."""
+        q = [np.ascontiguousarray(x, np.float32) for x in (pos, rot, vel, ang)]
+        cv, ca = np.zeros((self.N, 3), np.float32), np.zeros((self.N, 3), np.float32)
+        self._L.orc_contact_info(self.h, *[_p(x) for x in q], _p(cv), _p(ca))
+        return cv, ca
+
+    def physics_only(self, pos, rot, vel, ang, act):
+        """One env's physics step without any task code: the new (pos, rot, vel, ang) with the
+        frozen bodies' rows as given, and the unclipped contact terms (vel, ang), each (N, 3)."""
+        q = [np.array(x, np.float32, order="C") for x in (pos, rot, vel, ang)]
+        act = np.ascontiguousarray(act, np.float32)
+        cv, ca = np.zeros((self.N, 3), np.float32), np.zeros((self.N, 3), np.float32)
+        self._L.orc_physics_only(self.h, *[_p(x) for x in q], _p(act), _p(cv), _p(ca))
+        return q, (cv, ca)
+
+    def joint_angle_vel(self, pos, rot, vel, ang):
+        """sys.joints[0].angle_vel of one env's state: (angles (8,), velocities (8,))."""
+        q = [np.ascontiguousarray(x, np.float32) for x in (pos, rot, vel, ang)]
+        a, v = np.zeros(8, np.float32), np.zeros(8, np.float32)
+        self._L.orc_joint_angle_vel(self.h, *[_p(x) for x in q], _p(a), _p(v))
+        return a, v
+
 
 def split(key, n):
     key = np.ascontiguousarray(key, np.uint32)
@@ -343,8 +368,9 @@ def mesh_contacts(wall, a, b, seg: bool, r: float) -> np.ndarray:
 
 
 def math_check(op: int, a: np.ndarray, b: np.ndarray = None) -> np.ndarray:
-    """The spec's atan2f (op 0: atan2f(a, b)) or substep quaternion normalisation (op 1:
-    rows of a (n, 4)) as the oracle computes them."""
+    """The spec's atan2f (op 0: atan2f(a, b)), substep quaternion normalisation (op 1: rows of
+    a (n, 4)) or quaternion product (op 2: rows of a (n, 4) times rows of b (n, 4)) as the oracle
+    computes them."""
     a = np.ascontiguousarray(a, np.float32)
     n = a.shape[0]
     b = np.ascontiguousarray(b if b is not None else np.zeros(n), np.float32)

@@ -201,11 +201,17 @@ static float orc_atan2f(float y, float x) {
 }
 /* Test hook for the spec's elementary functions (tests/test_oracle_golden.py):
  * op 0: out[i] = orc_atan2f(a[i], b[i]); op 1: the substep normalisation of the quaternions
- * a[4i..4i+3] into out[4i..4i+3]. */
+ * a[4i..4i+3] into out[4i..4i+3]; op 2: qmul of the quaternions a[4i..] and b[4i..] (the
+ * task-logic stand-in's brax.math.quat_mul, oracle/ref_standin.py). */
 void orc_math_check(int op, int n, const float *a, const float *b, float *out) {
   for (int i = 0; i < n; ++i) {
     if (op == 0) out[i] = orc_atan2f(a[i], b[i]);
-    else {
+    else if (op == 2) {
+      q4 u = {a[4 * i], a[4 * i + 1], a[4 * i + 2], a[4 * i + 3]};
+      q4 v = {b[4 * i], b[4 * i + 1], b[4 * i + 2], b[4 * i + 3]};
+      q4 r = qmul(u, v);
+      out[4 * i] = r.w; out[4 * i + 1] = r.x; out[4 * i + 2] = r.y; out[4 * i + 3] = r.z;
+    } else {
       q4 q = {a[4 * i], a[4 * i + 1], a[4 * i + 2], a[4 * i + 3]};
       q4 r = qnormalize(q);
       out[4 * i] = r.w; out[4 * i + 1] = r.x; out[4 * i + 2] = r.y; out[4 * i + 3] = r.z;
@@ -1731,6 +1737,28 @@ static void angle_vel(const orc_env *e, const body_t *b, float *angle, float *av
     angle[j] = orc_atan2f(vdot(vcross(fp, fc), ap), vdot(fp, fc));
     avel[j] = vdot(vsub(b->w[c], b->w[p]), ap);
   }
+}
+
+/* test hooks for the task-logic stand-in (oracle/ref_standin.py): the physics of one env's step
+ * alone -- what step_one runs before any task code -- in place on pos/rot/vel/ang (the frozen
+ * bodies' rows are left as they are), the unclipped contact terms (N, 3) out; and the joint
+ * angles and velocities of a state */
+void orc_physics_only(const orc_env *e, float *pos, float *rot, float *vel, float *ang, const float *act,
+                      float *cvel, float *cang) {
+  body_t b; load_body(e, pos, rot, vel, ang, &b);
+  v3 cv[NDYN], ca[NDYN];
+  physics_step(e, &b, act, cv, ca);
+  store_body(&b, pos, rot, vel, ang);
+  for (int i = 0; i < e->N; ++i) {
+    float *o = cvel + 3 * i, *a = cang + 3 * i;
+    if (i < NDYN) { o[0] = cv[i].x; o[1] = cv[i].y; o[2] = cv[i].z; a[0] = ca[i].x; a[1] = ca[i].y; a[2] = ca[i].z; }
+    else { o[0] = o[1] = o[2] = a[0] = a[1] = a[2] = 0.0f; }
+  }
+}
+void orc_joint_angle_vel(const orc_env *e, const float *pos, const float *rot, const float *vel,
+                         const float *ang, float *angle, float *avel) {
+  body_t b; load_body(e, pos, rot, vel, ang, &b);
+  angle_vel(e, &b, angle, avel);
 }
 
 /* the 29 + 6N shared prefix (ant_*.py _get_obs).  With sh = -2 it is the stock ant's

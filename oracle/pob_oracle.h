@@ -104,8 +104,16 @@ void orc_set_face_cull(int on);
  * triangle point, 8 brax's closest-point forms (pob_oracle.c MV_*) */
 void orc_set_mesh_variant(int v);
 int orc_get_mesh_variant(void);
-/* test hook: op 0 atan2f(a, b); op 1 substep quaternion normalisation of a (n x 4) */
+/* test hook: op 0 atan2f(a, b); op 1 substep quaternion normalisation of a (n x 4); op 2 the
+ * quaternion product of a and b (n x 4 each) */
 void orc_math_check(int op, int n, const float *a, const float *b, float *out);
+/* test hooks for the task-logic stand-in (oracle/ref_standin.py): one env's physics step alone, in
+ * place on pos/rot/vel/ang (N rows; frozen rows untouched), unclipped contact terms (N, 3) out;
+ * sys.joints[0].angle_vel of a state (8 angles, 8 velocities) */
+void orc_physics_only(const orc_env *e, float *pos, float *rot, float *vel, float *ang, const float *act,
+                      float *cvel, float *cang);
+void orc_joint_angle_vel(const orc_env *e, const float *pos, const float *rot, const float *vel,
+                         const float *ang, float *angle, float *avel);
 
 /* RNG (jax threefry, pre-partitionable) */
 void orc_threefry2x32(const uint32_t key[2], uint32_t x0, uint32_t x1, uint32_t out[2]);
