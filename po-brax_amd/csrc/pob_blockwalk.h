@@ -122,7 +122,7 @@ POB_BW_D void bw_body_ranges(const int base, const int n0, const int n1, const i
   c[3] = ovf ? c[0] : c[2] + 2 * n2;
 }
 
-// The torso's items once per lane quad (pob_quad.h POB_QUAD_TORSO_ONCE): the four lanes of a
+// The torso's items once per lane quad (pob_quad.h qwalls_detect_block): the four lanes of a
 // quad (lanes 4 e .. 4 e + 3 of a wave: one env) hold bit-identical replicas of the torso, so
 // only the quad's lane 0 counts and publishes the torso's items -- n0 of them, from its own
 // base base0 on -- and all four lanes apply the torso's contacts from those slots.
@@ -142,7 +142,7 @@ POB_BW_D void bw_quad_ranges(const int lane, const int base0, const int n0, cons
   c[4] = ovf ? c[2] : c[3] + 2 * n2;
 }
 
-// One hit scan per collide substep (pob_quad.h POB_QUAD_HIT_MASK): after the evaluation a lane
+// One hit scan per collide substep (pob_quad.h qwalls_detect_block): after the evaluation a lane
 // reads the two dist words of each item of a body once and keeps "triangle t of the body's item
 // i holds a contact" as bit 2 i + t of a 32-bit mask; both apply passes walk the mask's set bits
 // (contact slot = the body's first slot + the bit's number), lowest first: the walk order.  A

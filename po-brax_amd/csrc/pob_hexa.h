@@ -77,22 +77,17 @@ struct HGround {
   float pen;
   v3 pe;  // x + rotate(end, q)
 };
-// (POB_HEX_POOL, the default since round 6: the wave's contacts in an LDS pool, stored by the
-// walk's winner lanes and linked per lane by the owners -- HH B = 4 096 0.0596 -> 0.0563 ms,
-// 8 192 0.0699 -> 0.0672, profiles/r7g/ab.txt; 0: the per-lane store with its hand-over loop)
-#ifndef POB_HEX_POOL
-#define POB_HEX_POOL 1
-#endif
+// (Since round 6 the wave's contacts live in an LDS pool, stored by the walk's winner lanes and
+// linked per lane by the owners.  The variant it replaced, since removed, was a per-lane store
+// with a hand-over loop: HH B = 4 096 0.0596 -> 0.0563 ms, 8 192 0.0699 -> 0.0672,
+// profiles/r7g/ab.txt.)
 struct HMesh {
   v3 a, b;
   uint64_t mc;
-  int nct;  // wall contacts of the position pass (the first HMAXC kept in the lane's LDS store)
-#if POB_HEX_POOL
-  int head;   // the lane's first contact in the wave's pool (POB_HEX_POOL)
+  int nct;  // wall contacts of the position pass
+  int head;   // the lane's first contact in the wave's pool
   bool povf;  // the wave's contacts overflowed the pool (wave-uniform)
-#endif
 };
-#if POB_HEX_POOL
 // the wave's contact pool (pob_mesh.h mesh_wave_walk HAND 2, as the four-lane kernel's fast
 // launch): each entry tau, n, dist and the index of the lane's next entry (-1: the last)
 #define HPOOL_N 64
@@ -125,13 +120,9 @@ struct HPoolSink {
     }
   }
 };
-#endif
-// The position pass's wall contacts (tau, n, pen), kept in the lane's slots of the staging
-// region (idle during the substeps; lane-minor: element e of the lane at CS[64 e]) so that the
-// velocity pass applies them without evaluating their faces again; a lane with more re-walks
-// its contact faces (ms.mc) from the stored segments instead -- the same contacts either way.
-#define HMAXC 5
-#define HCS_FLOATS (5 * HMAXC)
+// The position pass's wall contacts stay in the pool so that the velocity pass applies them
+// without evaluating their faces again; a wave whose pool overflowed re-walks its lanes' contact
+// faces (ms.mc) from the stored segments instead -- the same contacts either way.
 
 // Contacts of a collide substep on one lane (oracle order: ground, then walls in wall / face /
 // triangle order).  Walls: the broadphase over the walls' grown boxes (registers, HWalls) by
@@ -152,18 +143,12 @@ POB_D void hcontacts_position(G &g, const HCon &SC, const float *HT, const float
   if (gc.pen > 0.0f) oground_position(g, SC, gc.pen, gc.pe, HT[HT_GR], im, b.x, b.q, pq, px, DX, DA);
   ms.mc = 0ull;
   ms.nct = 0;
-#if POB_HEX_POOL
   ms.head = -1;
   ms.povf = false;
-#endif
   if (MW == 0) return;
   uint32_t m = 0u;
   {
-#ifdef POB_EXP_NO_WALLS
-    const int nw = 0;  // timing experiment only
-#else
     const int nw = HW.n_walls;
-#endif
 #pragma unroll
     for (int w = 0; w < MW; ++w) {
       // every wall's box is tested (the table always holds POB_MAXW rows), w < nw a predicate
@@ -190,15 +175,10 @@ POB_D void hcontacts_position(G &g, const HCon &SC, const float *HT, const float
 #ifdef POB_EXP_TIMING_SUB
   if (tacc) tacc[5] += __builtin_amdgcn_s_memtime() - _tc0;
 #endif
-#ifdef POB_EXP_NO_WALK
-  return;  // timing experiment only: broadphase and face cull, no face walk
-#endif
-  // the walk only collects the contacts (its rounds hand each one to its owner lane: a store of
-  // five floats); the position responses follow from the store in walk order, one loop over
-  // the lanes' contacts instead of the response code in every round's hand-over
+  // the walk only collects the contacts (its winner lanes store each one in the wave's pool, CS,
+  // and the owners link them); the position responses follow from the pool in walk order, one
+  // loop over the lanes' contacts instead of the response code in every round's hand-over
   uint64_t Ms[1] = {M};
-#if POB_HEX_POOL
-  // (CS: the wave's pool)
   HPoolSink sink{CS, 0, -1, -1, 0, 0ull};
 #ifdef POB_EXP_TIMING_SUB
   const unsigned long long _tw0 = __builtin_amdgcn_s_memtime();  // (slot 3: the walk alone)
@@ -226,30 +206,6 @@ POB_D void hcontacts_position(G &g, const HCon &SC, const float *HT, const float
       }
     }
   }
-#else
-  mesh_wave_walk<1, false>(g, WT, HW.fc, HW.cz, HW.hz, Ms,
-                    [&](const int, v3 &A, v3 &B, float &r, bool &seg) { A = ms.a; B = ms.b; r = HT[HT_R]; seg = !torso; },
-                    [&](const int, const int bit, const float tau, const v3 n, const float dist) {
-    ms.mc |= 1ull << bit;
-    if (ms.nct < HMAXC) {
-      float *c = CS + 64 * 5 * ms.nct;
-      c[0] = tau; c[64] = n.x; c[128] = n.y; c[192] = n.z; c[256] = dist;
-    }
-    ++ms.nct;
-  });
-  const bool ovf = ms.nct > HMAXC;
-  const int nc = ovf ? 0 : ms.nct;
-#pragma unroll 1
-  for (int i = 0; i < HMAXC; ++i) {
-    if (!__any(i < nc)) break;
-    if (i < nc) {
-      // penetration r - dist; the contact at the triangle point pe - (1e-6 + dist) n
-      const float *c = CS + 64 * 5 * i;
-      owall_position(g, SC, HT[HT_R] - c[256], vfma(rv, c[0], b.x), V(c[64], c[128], c[192]), 1e-6f + c[256], im, b.x,
-                     b.q, pq, px, DX, DA);
-    }
-  }
-#endif
   if (!__any(ovf)) return;
   // (rare) more contacts than the store holds: the contact faces walked again, each contact
   // applied as it comes (the same contacts in the same order)
@@ -270,7 +226,6 @@ POB_D void hcontacts_velocity(G &g, const HCon &SC, const float *HT, const float
     ocontact_vel_one(g, SC, true, gc.pen, HTV(HT, HT_GE), V(0.0f, 0.0f, 1.0f), HT[HT_GR], im, b.x, b.q, b.v, b.w, dV, dW);
   if (MW == 0 || !__any(ms.nct != 0)) return;
   const v3 rv = qrot_xy(HTV(HT, HT_E0), b.q);
-#if POB_HEX_POOL
   const bool ovf = ms.povf && ms.nct > 0;
   {
     int ci = ms.povf || ms.nct == 0 ? -1 : ms.head;
@@ -284,19 +239,6 @@ POB_D void hcontacts_velocity(G &g, const HCon &SC, const float *HT, const float
       }
     }
   }
-#else
-  const bool ovf = ms.nct > HMAXC;
-  const int n = ovf ? 0 : ms.nct;
-#pragma unroll 1
-  for (int i = 0; i < HMAXC; ++i) {
-    if (!__any(i < n)) break;
-    if (i < n) {
-      const float *c = CS + 64 * 5 * i;
-      ocontact_vel_pe(g, SC, false, HT[HT_R] - c[256], vfma(rv, c[0], b.x), V(c[64], c[128], c[192]), 1e-6f + c[256], im,
-                      b.x, b.v, b.w, dV, dW);
-    }
-  }
-#endif
   if (!__any(ovf)) return;
   uint64_t Ms[1] = {ovf ? ms.mc : 0ull};
   mesh_wave_walk<1, false>(g, WT, HW.fc, HW.cz, HW.hz, Ms,
@@ -308,7 +250,7 @@ POB_D void hcontacts_velocity(G &g, const HCon &SC, const float *HT, const float
 
 // One XPBD substep on an env's sixteen lanes (see the header comment for the split).
 // (HSUB_T: pob_octet.h)
-// CS: the lane's wall-contact store (HCS_FLOATS lane-minor slots of LDS, element e at CS[64 e])
+// CS: the wave's wall-contact pool (HPOOL_N entries of 6 floats in LDS)
 template <int MW, class G>
 POB_D void hpbd_substep(G &g, csys_t &S, const float *HT, const float *WT, const HWalls<MW> &HW, HBody &b,
                         const float act, v3 &cv, v3 &ca, const bool COLLIDE, float *CS,

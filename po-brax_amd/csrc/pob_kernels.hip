@@ -26,15 +26,6 @@
 
 #include "../../include/pob.h"
 
-#ifndef POB_QUAD_PRIO  // the four-lane kernel's falling issue priority over the substeps (k_step_quad)
-#define POB_QUAD_PRIO 1
-#endif
-#ifndef POB_OCT_PRIO  // the same in the eight-lane kernel's branch-guard build (two waves per SIMD)
-#define POB_OCT_PRIO 1
-#endif
-#ifndef POB_HEX_PRIO  // the same in the sixteen-lane kernel at two or more waves per SIMD:
-#define POB_HEX_PRIO 1  // HH B = 8 192 0.0669 -> 0.0630 ms, TAG 0.0490 -> 0.0461 (profiles/r7ab)
-#endif
 #include "pob_quad.h"
 #include "pob_octet.h"
 #include "pob_hexa.h"
@@ -548,9 +539,7 @@ POB_D void task_obs_write(const int kind, float *o, const int base, const TaskOu
 // and leg k (bodies 2k+1, 2k+2).  39 LDS floats / lane.  Lane 0 runs the per-env POMDP
 // tail; every lane writes its bodies' rows, its joints' obs and its cfrc rows.
 // gt = the quad-lane index within this env batch (4 b + k).
-#ifndef POB_QUAD_MIN_WAVES
 #define POB_QUAD_MIN_WAVES 4
-#endif
 // Per-wave LDS region: the block's per-lane scratch is laid out wave-major (wave w owns
 // floats [w * POB_STAGE_FLOATS, (w + 1) * POB_STAGE_FLOATS), element e of its lane t at
 // e * 64 + t: conflict-free), so a wave can reuse its whole region as a contiguous staging
@@ -777,7 +766,7 @@ __device__ __forceinline__ void quad_store_dyn(const StatePtrs &in, const StateP
 // * the per-wave kernels (AntGather, the mixed launch, one-wave blocks) keep the second launch
 //   (MODE 2: k_step_quad<.., 2> / k_step_mixed<.., 2> test the marks): with the call in them
 //   their fast loops spill (GA B = 65 536 0.1142 -> 0.2138 ms, mixed fp16 B = 32 768 0.1144 ->
-//   0.1186; POB_QUAD_FUSE_WAVE=1 builds that form).
+//   0.1186 -- a build variant, since removed).
 // The marks are a caller-provided scratch array (pob_state
 // ovf_mark, ABI v8) outside every output -- round 5's in-band mark (a signalling NaN in the
 // wave's first obs element) could be forged by a first_obs row that AUTORESET copies -- and
@@ -797,12 +786,22 @@ __device__ __forceinline__ void quad_store_dyn(const StatePtrs &in, const StateP
 // from the kernel's start to the call, and the fast loop spilled scalars around them -- 180
 // v_readlane in the HH kernel, which cost the whole gain of the dropped launch, HH B = 65 536
 // 0.1278 ms with and without it; profiles/r11a/ab.txt)
-#ifndef POB_QUAD_FUSE_WAVE
-#define POB_QUAD_FUSE_WAVE 0  // (1: the per-wave kernels call the fix-up too -- measured slower, above)
-#endif
 template <int KIND, typename QT>
 __device__ __attribute__((noinline)) void quad_fixup(const void *kargs, int gt, uint32_t stg_at, uint32_t lds_at,
                                                      uint32_t legtab_at);
+// Substep `it` of 2 * iters: issue priority falls with progress (3, 2, 1, 0 by quarter), so a
+// SIMD's waves (in the four-lane kernel four, one per block) advance together: with the
+// default oldest-first arbitration the first wave finishes early and the last one runs its
+// final substeps alone, at one-wave latency (measured per wave with POB_EXP_TIMING: p0..max of
+// the physics phase 94 K..211 K ticks before, 133 K..182 K with this; kernel 0.120 -> 0.112 ms
+// at B = 65 536).
+POB_D void substep_prio(const int it, const int iters) {
+  const int lvl = (it * 4) / (2 * iters);
+  if (lvl == 0) __builtin_amdgcn_s_setprio(3);
+  else if (lvl == 1) __builtin_amdgcn_s_setprio(2);
+  else if (lvl == 2) __builtin_amdgcn_s_setprio(1);
+  else __builtin_amdgcn_s_setprio(0);
+}
 typedef __attribute__((address_space(3))) float lds_float;
 POB_D uint32_t lds_addr(const float *p) { return (uint32_t)(size_t)(const lds_float *)p; }
 POB_D float *lds_ptr(const uint32_t at) { return (float *)(lds_float *)(size_t)at; }
@@ -842,15 +841,12 @@ POB_D void step_quad_body(csys_t *Sp, const int B, const StatePtrs &in, const fl
   // the same indices from an opaque copy of the thread index (after the substep loop: the copies
   // above are then dead across it, instead of held -- in practice spilled -- through it)
   // a marked wave's step, over again from its inputs: in this launch (FUSED), or left to the
-  // fix-up launch (POB_EXP_NO_FIXUP_LAUNCH, timing experiment only: neither -- valid where no
-  // wave is marked)
-  constexpr bool FUSED = MODE == 1 && (COOP || POB_QUAD_FUSE_WAVE);
+  // fix-up launch
+  constexpr bool FUSED = MODE == 1 && COOP;
   auto fixup = [&]() {
-#ifndef POB_EXP_NO_FIXUP_LAUNCH
     if constexpr (FUSED)
       quad_fixup<KIND, QT>((const void *)__builtin_amdgcn_kernarg_segment_ptr(), gt, lds_addr(stg), lds_addr(lds),
                            lds_addr(legtab));
-#endif
   };
   auto rederive = [&]() {
     int g2 = gt;
@@ -936,12 +932,7 @@ POB_D void step_quad_body(csys_t *Sp, const int B, const StatePtrs &in, const fl
 
   POB_TS(1);
   // ---- physics (10 substeps in registers + the lane's LDS slots)
-#ifndef POB_QUAD_TWO_PASS
-#define POB_QUAD_TWO_PASS 1
-#endif
-#ifndef POB_QUAD_NEAR_MARGIN
 #define POB_QUAD_NEAR_MARGIN 0.5f
-#endif
   float jang[QNJ], jvel[QNJ];
   v3 cvl[QNB], cal[QNB];
   TaskOut t;
@@ -958,12 +949,8 @@ POB_D void step_quad_body(csys_t *Sp, const int B, const StatePtrs &in, const fl
     // each instantiation reacts differently; profiles/r5x_ab.txt: HH B = 65 536 0.1873 ms with
     // neither, TAG 0.1176 with both, GA 0.1147 and mixed fp16 B = 32 768 0.1281 with the
     // re-derivation only; profiles/r5y_ab.txt)
-#ifndef POB_QUAD_FAST_PASS
 #define POB_QUAD_FAST_PASS 4
-#endif
-#ifndef POB_QUAD_REDERIVE
 #define POB_QUAD_REDERIVE 22
-#endif
     constexpr int KBIT = KIND < 0 ? 16 : 1 << KIND;
     constexpr bool FASTP = (POB_QUAD_FAST_PASS & KBIT) != 0, REDER = (POB_QUAD_REDERIVE & KBIT) != 0;
     if (LEG) {
@@ -971,13 +958,6 @@ POB_D void step_quad_body(csys_t *Sp, const int B, const StatePtrs &in, const fl
 #pragma nounroll
       for (int it = 0; it < Sp->substeps; ++it) qlegacy_substep<KIND != POB_ANT>(Sp, LT, WT, bd, a, Ls);
     } else {
-#if defined(POB_EXP_NO_COLLIDE)
-#pragma nounroll
-    for (int it = 0; it < 2 * iters; ++it) qpbd_substep<KIND != POB_ANT>(Sp, LT, WT, bd, a, Ls, false, S.friction);  // timing experiment only
-#elif defined(POB_EXP_NO_PHYSICS)
-#pragma nounroll
-    for (int it = 0; it < 0 * iters; ++it) qpbd_substep<KIND != POB_ANT>(Sp, LT, WT, bd, a, Ls, false, S.friction);  // timing experiment only
-#else
     // Two passes (wave-uniform): a wave whose lanes are all clear of the walls' broadphase boxes
     // (grown by POB_QUAD_NEAR_MARGIN) at the start of the step runs the substeps without the
     // wall code and checks the broadphase of every collide substep; if a lane met one, the wave
@@ -987,7 +967,7 @@ POB_D void step_quad_body(csys_t *Sp, const int B, const StatePtrs &in, const fl
     // (AntGather only: its ants start at the arena's centre, so whole waves run the no-wall
     // pass -- 0.272 -> 0.122 ms at B = 65 536; the HH / TAG waves nearly always hold an ant near
     // a wall, and the second copy of the substep loop costs them 5-10 %, profiles/r5m)
-    constexpr bool TWO = KIND == POB_GATHER && POB_QUAD_TWO_PASS;
+    constexpr bool TWO = KIND == POB_GATHER;
     constexpr bool WALLS = KIND != POB_ANT;
     // Wall passes (POB_QUAD_FAST_PASS, off): a fast pass keeping at most QK wall contacts per
     // lane and collide substep, a wave with more (rare) running the step again in the slow pass
@@ -1012,13 +992,7 @@ POB_D void step_quad_body(csys_t *Sp, const int B, const StatePtrs &in, const fl
       bool near = false;
 #pragma nounroll
       for (int it = 0; it < 2 * iters; ++it) {
-#if POB_QUAD_PRIO == 1
-        const int lvl = (it * 4) / (2 * iters);
-        if (lvl == 0) __builtin_amdgcn_s_setprio(3);
-        else if (lvl == 1) __builtin_amdgcn_s_setprio(2);
-        else if (lvl == 2) __builtin_amdgcn_s_setprio(1);
-        else __builtin_amdgcn_s_setprio(0);
-#endif
+        substep_prio(it, iters);
         qpbd_substep<false, true>(Sp, LT, WT, bd, a, Ls, (it & 1) != 0, fric, &near);
       }
       if (!__any(near)) break;
@@ -1027,9 +1001,6 @@ POB_D void step_quad_body(csys_t *Sp, const int B, const StatePtrs &in, const fl
       reload();
       continue;
     }
-#ifndef POB_QUAD_SLOW_OOL
-#define POB_QUAD_SLOW_OOL 1  // (with POB_QUAD_FAST_PASS: the slow pass's substep out of line)
-#endif
     if constexpr (MODE == 1 && WALLS && COOP) {
       // the fast pass, block-cooperative: every wave of the block runs every substep (two block
       // barriers in each collide substep, qwalls_detect_block) and only then leaves -- a wave past
@@ -1040,13 +1011,7 @@ POB_D void step_quad_body(csys_t *Sp, const int B, const StatePtrs &in, const fl
                  capf != 0 ? capf : QBW_CAP, hitf != 0 ? hitf : QBW_HIT_ITEMS, dead, false};
 #pragma nounroll
       for (int it = 0; it < 2 * iters; ++it) {
-#if POB_QUAD_PRIO == 1
-        const int lvl = (it * 4) / (2 * iters);
-        if (lvl == 0) __builtin_amdgcn_s_setprio(3);
-        else if (lvl == 1) __builtin_amdgcn_s_setprio(2);
-        else if (lvl == 2) __builtin_amdgcn_s_setprio(1);
-        else __builtin_amdgcn_s_setprio(0);
-#endif
+        substep_prio(it, iters);
         qpbd_substep<WALLS, false, false, true>(Sp, LT, WT, bd, a, Ls, (it & 1) != 0, fric, nullptr, nullptr, &blk);
       }
       if (dead) return;
@@ -1063,13 +1028,7 @@ POB_D void step_quad_body(csys_t *Sp, const int B, const StatePtrs &in, const fl
       bool ovf = false;
 #pragma nounroll
       for (int it = 0; it < 2 * iters; ++it) {
-#if POB_QUAD_PRIO == 1
-        const int lvl = (it * 4) / (2 * iters);
-        if (lvl == 0) __builtin_amdgcn_s_setprio(3);
-        else if (lvl == 1) __builtin_amdgcn_s_setprio(2);
-        else if (lvl == 2) __builtin_amdgcn_s_setprio(1);
-        else __builtin_amdgcn_s_setprio(0);
-#endif
+        substep_prio(it, iters);
         qpbd_substep<WALLS, false, false>(Sp, LT, WT, bd, a, Ls, (it & 1) != 0, fric, nullptr, &ovf);
         if (__any(ovf)) break;
       }
@@ -1084,18 +1043,7 @@ POB_D void step_quad_body(csys_t *Sp, const int B, const StatePtrs &in, const fl
       bool ovf = false;
 #pragma nounroll
       for (int it = 0; it < 2 * iters; ++it) {
-        // Issue priority falls with progress, so a SIMD's four waves (one per block) advance
-        // together: with the default oldest-first arbitration the first wave finishes early
-        // and the last one runs its final substeps alone, at one-wave latency (measured per
-        // wave with POB_EXP_TIMING: p0..max of the physics phase 94 K..211 K ticks before,
-        // 133 K..182 K with this; kernel 0.120 -> 0.112 ms at B = 65 536).
-#if POB_QUAD_PRIO == 1
-        const int lvl = (it * 4) / (2 * iters);
-        if (lvl == 0) __builtin_amdgcn_s_setprio(3);
-        else if (lvl == 1) __builtin_amdgcn_s_setprio(2);
-        else if (lvl == 2) __builtin_amdgcn_s_setprio(1);
-        else __builtin_amdgcn_s_setprio(0);
-#endif
+        substep_prio(it, iters);
         qpbd_substep<WALLS, false, false>(Sp, LT, WT, bd, a, Ls, (it & 1) != 0, fric, nullptr, &ovf);
         if (__any(ovf)) break;
       }
@@ -1107,14 +1055,7 @@ POB_D void step_quad_body(csys_t *Sp, const int B, const StatePtrs &in, const fl
     // the slow wall pass (after an overflow) / the stock ant (no walls)
 #pragma nounroll
     for (int it = 0; it < 2 * iters; ++it) {
-#if POB_QUAD_PRIO == 1
-      const int lvl = (it * 4) / (2 * iters);
-      if (lvl == 0) __builtin_amdgcn_s_setprio(3);
-      else if (lvl == 1) __builtin_amdgcn_s_setprio(2);
-      else if (lvl == 2) __builtin_amdgcn_s_setprio(1);
-      else __builtin_amdgcn_s_setprio(0);
-#endif
-#if POB_QUAD_SLOW_OOL
+      substep_prio(it, iters);
       if (WALLS && FASTP && MODE == 0) {
         QSlow st;
         st.b = bd;
@@ -1123,12 +1064,10 @@ POB_D void step_quad_body(csys_t *Sp, const int B, const StatePtrs &in, const fl
         qpbd_substep_slow<WALLS>(Sp, LT, WT, &st, Ls.base, Ls.t, (it & 1) != 0 ? 1 : 0, fric);
         bd = st.b;
       } else
-#endif
       qpbd_substep<WALLS>(Sp, LT, WT, bd, a, Ls, (it & 1) != 0, fric);
     }
     break;
     }
-#endif
     }
     if constexpr (REDER) rederive();
     // the torso's x at the step's start (the reward's displacement): loaded again (the state
@@ -1443,9 +1382,7 @@ __device__ __attribute__((noinline)) void quad_fixup(const void *kargs, int gt, 
   }
 }
 
-#ifndef POB_MIXED_MIN_WAVES
 #define POB_MIXED_MIN_WAVES 3  // config 5 runs 2 waves per SIMD: 170 VGPRs, no spills (128: 144 B of scratch, +6 %)
-#endif
 template <typename QT, int MODE = 0>
 __global__ __launch_bounds__(256, POB_MIXED_MIN_WAVES) void k_step_mixed(const MixArgs A, const uint32_t flags,
                                                                         const int L) {
@@ -1497,9 +1434,6 @@ __global__ __launch_bounds__(64) void k_step_oct(const void *sysp, const int B, 
   POB_TS(0);
   __shared__ float stg[POB_OSTAGE_FLOATS];
   __shared__ __attribute__((aligned(16))) float otab[OT_TAB_FLOATS + HW_FLOATS];
-#ifdef POB_FC_LDS
-  __shared__ __attribute__((aligned(16))) float ofc[POB_FC_TAB_FLOATS];  // the walls' face constants
-#endif
   csys_t *Sp = (csys_t *)(size_t)sysp;
   csys_t &S = *Sp;
   __shared__ float ocst[OCS_FLOATS * 64 + (oct_pool(KIND) ? 6 * OPOOL_N : 0)];  // the lanes' stores (then the wave's contact pool)
@@ -1584,9 +1518,6 @@ __global__ __launch_bounds__(64) void k_step_oct(const void *sysp, const int B, 
     const __attribute__((address_space(4))) float *wsrc = &Sp->wall_row[0][0];
     stage_table<POB_MAXW * POB_WALL_FLOATS>(otab + 8 * OT_FLOATS, wsrc, (int)threadIdx.x, 64);
     hwalls_stage(S, otab + OT_TAB_FLOATS, lane);  // the walls' broadphase boxes, z extent, scalars
-#ifdef POB_FC_LDS
-    stage_table<POB_FC_TAB_FLOATS>(ofc, &Sp->face_c[0][0][0], (int)threadIdx.x, 64);
-#endif
     wave_lds_sync();
   }
   float OT[OT_FLOATS];  // the lane's role row, in registers (constant indices only)
@@ -1595,11 +1526,7 @@ __global__ __launch_bounds__(64) void k_step_oct(const void *sysp, const int B, 
   const float *WT = otab + 8 * OT_FLOATS;
   constexpr int OMW = hex_max_walls(KIND);
   HWalls<OMW> HW;  // the walls in VGPRs (LDS loads: the compiler keeps them per lane)
-#ifdef POB_FC_LDS
-  hwalls_load(otab + OT_TAB_FLOATS, HW, ofc);
-#else
   hwalls_load(otab + OT_TAB_FLOATS, HW, pob_face_table(S));
-#endif
   POB_TS(1);
 
   // ---- physics (10 substeps in registers)
@@ -1622,13 +1549,6 @@ __global__ __launch_bounds__(64) void k_step_oct(const void *sysp, const int B, 
 #pragma unroll
     for (int sl = 0; sl < ONB; ++sl) { cvl[sl] = V(0.0f, 0.0f, 0.0f); cal[sl] = V(0.0f, 0.0f, 0.0f); }
     const int iters = Sp->substeps / 2;
-#if defined(POB_EXP_NO_COLLIDE)
-    GuardBranch gb;
-    for (int it = 0; it < 2 * iters; ++it) opbd_substep<OMW, oct_pool(KIND)>(gb, Sp, OT, WT, HW, isA, bd, a, cvl, cal, false, ocs);  // timing experiment only
-#elif defined(POB_EXP_NO_PHYSICS)
-    GuardBranch gb;
-    for (int it = 0; it < 0 * iters; ++it) opbd_substep<OMW, oct_pool(KIND)>(gb, Sp, OT, WT, HW, isA, bd, a, cvl, cal, false, ocs);  // timing experiment only
-#else
 #ifdef POB_EXP_TIMING_SUB  // timing experiment only: phase durations into stamps 5..12
 #define OCT_SUBSTEPS(G)                                                                       \
   _Pragma("nounroll") for (int it = 0; it < 2 * iters; ++it)                                 \
@@ -1639,13 +1559,7 @@ __global__ __launch_bounds__(64) void k_step_oct(const void *sysp, const int B, 
 // GA -0.5 % (profiles/r3t/oct_prio_ab.txt); a lone wave per SIMD has no one to yield to.
 #define OCT_SUBSTEPS(G)                                                                       \
   _Pragma("nounroll") for (int it = 0; it < 2 * iters; ++it) {                               \
-    if (!GACC && POB_OCT_PRIO) {                                                               \
-      const int lvl_ = (it * 4) / (2 * iters);                                                 \
-      if (lvl_ == 0) __builtin_amdgcn_s_setprio(3);                                            \
-      else if (lvl_ == 1) __builtin_amdgcn_s_setprio(2);                                       \
-      else if (lvl_ == 2) __builtin_amdgcn_s_setprio(1);                                       \
-      else __builtin_amdgcn_s_setprio(0);                                                      \
-    }                                                                                          \
+    if (!GACC) substep_prio(it, iters);                                                        \
     opbd_substep<OMW, oct_pool(KIND)>(G, Sp, OT, WT, HW, isA, bd, a, cvl, cal, (it & 1) != 0, ocs);                \
   }
 #endif
@@ -1668,7 +1582,6 @@ __global__ __launch_bounds__(64) void k_step_oct(const void *sysp, const int B, 
       }
     }
 #undef OCT_SUBSTEPS
-#endif
     {  // joint angle / velocity obs of the lane's joint (a3)
       const v3 ap = qrot(OTV(OT, OT_AXIS), bd.q[0]);
       const v3 ref = OTV(OT, OT_REF);
@@ -1840,33 +1753,23 @@ __global__ __launch_bounds__(64) void k_step_oct(const void *sysp, const int B, 
 // block; lane r of an env owns one body and one side of one joint (P_hip_r / C_hip_(7-r) /
 // P_knee_(r-8) / C_knee_(15-r)).  Lane 0 (P_hip_0, the torso) runs the per-env POMDP tail.
 #define POB_HSTAGE_FLOATS (OL_FLOATS * 64)
-static_assert(POB_HSTAGE_FLOATS >= HCS_FLOATS * 64, "the sixteen-lane staging region holds the wall-contact store");
-#ifndef POB_HEX_MINW  // experiment: the register budget of this many waves per SIMD
-#define POB_HEX_MINW 1
-#endif
-// PRIO: the falling issue priority over the substeps (POB_HEX_PRIO), launched from two waves
-// per SIMD on (at one wave per SIMD it only costs: HH B = 4 096 0.0563 -> 0.0574 ms, profiles/r7ac)
+// PRIO: the falling issue priority over the substeps (substep_prio), launched from two waves
+// per SIMD on: HH B = 8 192 0.0669 -> 0.0630 ms, TAG 0.0490 -> 0.0461 (profiles/r7ab); at one
+// wave per SIMD it only costs: HH B = 4 096 0.0563 -> 0.0574 ms (profiles/r7ac)
 template <int KIND, typename QT, bool GACC, bool PRIO = false>
-__global__ __launch_bounds__(64, POB_HEX_MINW) void k_step_hex(const void *sysp, const int B, const StatePtrs in,
-                                                 const float *__restrict__ act, const StatePtrs out,
-                                                 const uint32_t flags, const int L) {
+__global__ __launch_bounds__(64, 1) void k_step_hex(const void *sysp, const int B, const StatePtrs in,
+                                                    const float *__restrict__ act, const StatePtrs out,
+                                                    const uint32_t flags, const int L) {
   static_assert(KIND != POB_MIXED, "the sixteen-lane kernel runs one env kind per launch");
   POB_TS_DECL();  // timing experiment only (POB_EXP_TIMING)
   POB_TS(0);
   __shared__ float stg[POB_HSTAGE_FLOATS];
   __shared__ __attribute__((aligned(16))) float htab[HT_TAB_FLOATS + HW_FLOATS];
-#ifdef POB_FC_LDS
-  __shared__ __attribute__((aligned(16))) float hfc[POB_FC_TAB_FLOATS];  // the walls' face constants
-#endif
   csys_t *Sp = (csys_t *)(size_t)sysp;
   csys_t &S = *Sp;
   const int lane = (int)threadIdx.x;
-#if POB_HEX_POOL
   __shared__ float hpool[6 * HPOOL_N];
-  float *const hcs = hpool;  // the wave's wall-contact pool (pob_hexa.h POB_HEX_POOL)
-#else
-  float *const hcs = stg + lane;  // the lane's wall-contact store during the substeps (pob_hexa.h)
-#endif
+  float *const hcs = hpool;  // the wave's wall-contact pool (pob_hexa.h HPoolSink)
   const int r = lane & 15;
   const bool hip = r < 8, isP = r < 4 || (r >= 8 && r < 12);
   const int k = r < 4 ? r : (r < 8 ? 7 - r : (r < 12 ? r - 8 : 15 - r));  // the leg
@@ -1934,9 +1837,6 @@ __global__ __launch_bounds__(64, POB_HEX_MINW) void k_step_hex(const void *sysp,
     const __attribute__((address_space(4))) float *wsrc = &Sp->wall_row[0][0];
     stage_table<POB_MAXW * POB_WALL_FLOATS>(htab + 16 * HT_FLOATS, wsrc, (int)threadIdx.x, 64);
     hwalls_stage(S, htab + HT_TAB_FLOATS, lane);  // the walls' broadphase boxes, z extent, scalars
-#ifdef POB_FC_LDS
-    stage_table<POB_FC_TAB_FLOATS>(hfc, &Sp->face_c[0][0][0], (int)threadIdx.x, 64);
-#endif
     wave_lds_sync();
   }
   float HT[HT_FLOATS];  // the lane's role row, in registers (constant indices only)
@@ -1944,11 +1844,7 @@ __global__ __launch_bounds__(64, POB_HEX_MINW) void k_step_hex(const void *sysp,
   for (int i = 0; i < HT_FLOATS; ++i) HT[i] = htab[r * HT_FLOATS + i];
   const float *WT = htab + 16 * HT_FLOATS;
   HWalls<HMW> HW;  // the walls in VGPRs (LDS loads: the compiler keeps them per lane)
-#ifdef POB_FC_LDS
-  hwalls_load(htab + HT_TAB_FLOATS, HW, hfc);
-#else
   hwalls_load(htab + HT_TAB_FLOATS, HW, pob_face_table(S));
-#endif
   POB_TS(1);
 
   // ---- physics (10 substeps in registers)
@@ -1969,33 +1865,14 @@ __global__ __launch_bounds__(64, POB_HEX_MINW) void k_step_hex(const void *sysp,
     const float xb = bd.x.x;
     const float a = a_in;
     const int iters = Sp->substeps / 2;
-#if defined(POB_EXP_NO_COLLIDE)
-    GuardBranch gb;
-    for (int it = 0; it < 2 * iters; ++it) hpbd_substep<hex_max_walls(KIND)>(gb, S, HT, WT, HW, bd, a, cvl, cal, false, hcs);  // timing experiment only
-#elif defined(POB_EXP_NO_PHYSICS)
-    GuardBranch gb;
-    for (int it = 0; it < 0 * iters; ++it) hpbd_substep<hex_max_walls(KIND)>(gb, S, HT, WT, HW, bd, a, cvl, cal, false, hcs);  // timing experiment only
-#else
-#ifdef POB_HEX_UNROLL2
-#define HEX_SUBSTEPS(G)                                                                       \
-  _Pragma("nounroll") for (int it = 0; it < iters; ++it) {                                   \
-    hpbd_substep<hex_max_walls(KIND)>(G, S, HT, WT, HW, bd, a, cvl, cal, false, hcs);                  \
-    hpbd_substep<hex_max_walls(KIND)>(G, S, HT, WT, HW, bd, a, cvl, cal, true, hcs);                   \
-  }
-#elif defined(POB_EXP_TIMING_SUB)  // timing experiment only: phase durations into stamps 5..12
+#ifdef POB_EXP_TIMING_SUB  // timing experiment only: phase durations into stamps 5..12
 #define HEX_SUBSTEPS(G)                                                                       \
   _Pragma("nounroll") for (int it = 0; it < 2 * iters; ++it)                                 \
     hpbd_substep<hex_max_walls(KIND)>(G, S, HT, WT, HW, bd, a, cvl, cal, (it & 1) != 0, hcs, pob_ts + 5);
 #else
 #define HEX_SUBSTEPS(G)                                                                       \
   _Pragma("nounroll") for (int it = 0; it < 2 * iters; ++it) {                               \
-    if constexpr (PRIO) {                                                                    \
-      const int lvl_ = (it * 4) / (2 * iters);                                               \
-      if (lvl_ == 0) __builtin_amdgcn_s_setprio(3);                                          \
-      else if (lvl_ == 1) __builtin_amdgcn_s_setprio(2);                                     \
-      else if (lvl_ == 2) __builtin_amdgcn_s_setprio(1);                                     \
-      else __builtin_amdgcn_s_setprio(0);                                                    \
-    }                                                                                        \
+    if constexpr (PRIO) substep_prio(it, iters);                                             \
     hpbd_substep<hex_max_walls(KIND)>(G, S, HT, WT, HW, bd, a, cvl, cal, (it & 1) != 0, hcs); \
   }
 #endif
@@ -2016,7 +1893,6 @@ __global__ __launch_bounds__(64, POB_HEX_MINW) void k_step_hex(const void *sysp,
       HEX_SUBSTEPS(gb)
     }
     }
-#endif
     {  // joint angle / velocity obs of the lane's joint (a3), on both of its lanes
       const q4 qo = hx_pair4(bd.q);
       const v3 wo = hx_pair3(bd.w);
@@ -2994,7 +2870,7 @@ template <typename QT, bool GACC>
 static void launch_step_hex_g(int kind, hipStream_t st, const void *sp, int B, const StatePtrs &pi, const float *act,
                               const StatePtrs &po, uint32_t flags, int L, int n_cu) {
   const dim3 g((unsigned)((B + 3) / 4)), b(64);
-  if (POB_HEX_PRIO && (B + 3) / 4 > 4 * n_cu) {  // two or more waves per SIMD (HH and TAG run that far)
+  if ((B + 3) / 4 > 4 * n_cu) {  // two or more waves per SIMD (HH and TAG run that far)
     if (kind == POB_HEAVENHELL) {
       hipLaunchKernelGGL((k_step_hex<POB_HEAVENHELL, QT, GACC, true>), g, b, 0, st, sp, B, pi, act, po, flags, L);
       return;
@@ -3054,16 +2930,7 @@ static void launch_step_oct(int kind, int n_cu, hipStream_t st, const void *sp, 
 // (profiles/r6b_ab.txt, r6c_ab.txt); since round 6's LDS contact pool (no scratch in the fast
 // launch) the mixed launch too: fp16 B = 32 768 0.1231 -> 0.1149 ms (profiles/r7h).
 // POB_QUAD_SPLIT=0 forces the one-pass kernel, any other value the fast pass with its fix-up.
-// (the fix-up launch after a per-wave fast launch; POB_EXP_NO_FIXUP_LAUNCH, timing experiment
-// only: no fix-up at all, launched or called -- valid where no wave is marked)
-#ifdef POB_EXP_NO_FIXUP_LAUNCH
-#define POB_FIXUP_LAUNCH 0
-#else
-#define POB_FIXUP_LAUNCH (!POB_QUAD_FUSE_WAVE)
-#endif
-#ifndef POB_QUAD_SPLIT_KINDS
 #define POB_QUAD_SPLIT_KINDS 23
-#endif
 static bool quad_split_launch(int kind) {
   const char *f = getenv("POB_QUAD_SPLIT");
   if (f) return atoi(f) != 0;
@@ -3112,7 +2979,7 @@ static void launch_step_quad(int kind, bool legacy, int n_cu, hipStream_t st, co
   // 256-thread blocks of HH / TAG: the fast pass's block-cooperative wall walk
   const bool coop = split && bs == 256 && (kind == POB_HEAVENHELL || kind == POB_TAG);
   flags |= coop ? quad_block_cap() | quad_hit_width() : 0u;
-  const bool second = split && !coop && POB_FIXUP_LAUNCH;  // the fix-up launch
+  const bool second = split && !coop;  // the fix-up launch
   switch (kind) {
     case POB_HEAVENHELL:
       if (split) {
@@ -3345,10 +3212,10 @@ int pob_step_mixed(int n, pob_env *const *envs, const int *B, const pob_state *i
     flags |= quad_force_fixup();
     if (envs[0]->sys.qp_f16) {
       hipLaunchKernelGGL((k_step_mixed<__half, 1>), g, dim3(256), 0, st, A, flags, episode_length);
-      if (POB_FIXUP_LAUNCH) hipLaunchKernelGGL((k_step_mixed<__half, 2>), g, dim3(256), 0, st, A, flags, episode_length);
+      hipLaunchKernelGGL((k_step_mixed<__half, 2>), g, dim3(256), 0, st, A, flags, episode_length);
     } else {
       hipLaunchKernelGGL((k_step_mixed<float, 1>), g, dim3(256), 0, st, A, flags, episode_length);
-      if (POB_FIXUP_LAUNCH) hipLaunchKernelGGL((k_step_mixed<float, 2>), g, dim3(256), 0, st, A, flags, episode_length);
+      hipLaunchKernelGGL((k_step_mixed<float, 2>), g, dim3(256), 0, st, A, flags, episode_length);
     }
   } else if (envs[0]->sys.qp_f16) {
     hipLaunchKernelGGL((k_step_mixed<__half>), g, dim3(256), 0, st, A, flags, episode_length);

@@ -17,15 +17,13 @@
 // gap >= r + 1e-3 along some axis between the face rectangle and the segment's bounding box
 // means no triangle of the face is within r).
 #pragma once
-#include <type_traits>
 #include "pob_math.h"
 
 #define POB_MESH_MARGIN 1e-3f
 // the face constants table (pob_sys::face_c) is read through the constant address space
-// (POB_FC_LDS: a generic pointer -- the eight- and sixteen-lane kernels pass their LDS copy of
-// the table, the four-lane kernel the device table; the compiler infers each one's address
-// space through the inlined walk)
-#if defined(POB_MESH_HOST) || defined(POB_FC_LDS)
+// (a variant tried and removed: the eight- and sixteen-lane kernels' LDS copy of the table
+// through a generic pointer -- HH B = 4 096 -0.7 %, GA B = 16 384 +2.6 %)
+#ifdef POB_MESH_HOST
 typedef const float *fcptr_t;
 #else
 typedef __attribute__((address_space(4))) const float *fcptr_t;
@@ -82,7 +80,7 @@ POB_D uint32_t mesh_face_mask(const v3 A, const v3 B, const float hx, const floa
 // of the four squared distances (ties averaged), the normal (S - P) / (1e-6 + |S - P|), the
 // contact at the triangle point.  The same operations on the same operands as the oracle;
 // jp.clip as selects (bclamp01 / bclamps: the same bits for -0 and NaN on both sides).
-#if defined(POB_MESH_HOST) || defined(POB_MESH_NO_MFENCE)
+#ifdef POB_MESH_HOST
 #define MFENCE() ((void)0)
 #else
 #define MFENCE() __builtin_amdgcn_sched_barrier(0)
@@ -205,39 +203,15 @@ struct MFace {
   float sg, ha, hb, w0, ha2, hb2;
   BSeg A;          // the capsule's segment
   fcptr_t fc;      // the face's constants (POB_FC_*)
-#if defined(POB_MESH_FC_INLINE) || defined(POB_MESH_FC_VEC)
-  // (A/B build switches: the constants formed per face evaluation, or the face's row loaded
-  // whole -- three 16-B loads -- and each lane's class picked by selects instead of per-lane
-  // scattered loads)
-  float cv[POB_FACE_FLOATS];
-#endif
 };
 // the face's constants: edge class c's (il, hl, idd), the diagonal's d.d, triangle t's 1 / det
 POB_D void mfc_edge(const MFace &F, const int c, float &il, float &hl, float &idd) {
-#if defined(POB_MESH_FC_INLINE) || defined(POB_MESH_FC_VEC)
-  il = c == 0 ? F.cv[POB_FC_IL(0)] : (c == 1 ? F.cv[POB_FC_IL(1)] : F.cv[POB_FC_IL(2)]);
-  hl = c == 0 ? F.cv[POB_FC_HL(0)] : (c == 1 ? F.cv[POB_FC_HL(1)] : F.cv[POB_FC_HL(2)]);
-  idd = c == 0 ? F.cv[POB_FC_IDD(0)] : (c == 1 ? F.cv[POB_FC_IDD(1)] : F.cv[POB_FC_IDD(2)]);
-#else
   il = F.fc[POB_FC_IL(c)];
   hl = F.fc[POB_FC_HL(c)];
   idd = F.fc[POB_FC_IDD(c)];
-#endif
 }
-POB_D float mfc_ed(const MFace &F) {
-#if defined(POB_MESH_FC_INLINE) || defined(POB_MESH_FC_VEC)
-  return F.cv[POB_FC_ED];
-#else
-  return F.fc[POB_FC_ED];
-#endif
-}
-POB_D float mfc_idet(const MFace &F, const int t) {
-#if defined(POB_MESH_FC_INLINE) || defined(POB_MESH_FC_VEC)
-  return t == 0 ? F.cv[POB_FC_IDET(0)] : F.cv[POB_FC_IDET(1)];
-#else
-  return F.fc[POB_FC_IDET(t)];
-#endif
-}
+POB_D float mfc_ed(const MFace &F) { return F.fc[POB_FC_ED]; }
+POB_D float mfc_idet(const MFace &F, const int t) { return F.fc[POB_FC_IDET(t)]; }
 // the capsule's segment in the wall frame (once per wall; oracle capsule_wall_mesh capw)
 template <class G>
 POB_D BSeg mcap_seg(G &g, const v3 La, const v3 Lb) {
@@ -258,39 +232,6 @@ POB_D MFace mface(G &g, const int f, const BSeg &capw, const float hx, const flo
   F.ha2 = F.ha + F.ha;  // V1 - V0 = (ha - (-ha), ..): exact
   F.hb2 = F.hb + F.hb;
   F.fc = fcw + POB_FACE_FLOATS * k;
-#ifdef POB_MESH_FC_VEC
-#ifdef POB_MESH_HOST
-  for (int i = 0; i < POB_FACE_FLOATS; ++i) F.cv[i] = F.fc[i];
-#else
-  static_assert(POB_FACE_FLOATS == 12, "three 16-B loads per face row");
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    typedef float f4v __attribute__((ext_vector_type(4)));
-#ifdef POB_FC_LDS
-    const f4v q = reinterpret_cast<const f4v *>(F.fc)[i];
-#else
-    const f4v q = reinterpret_cast<const __attribute__((address_space(4))) f4v *>(F.fc)[i];
-#endif
-    F.cv[4 * i] = q.x; F.cv[4 * i + 1] = q.y; F.cv[4 * i + 2] = q.z; F.cv[4 * i + 3] = q.w;
-  }
-#endif
-#endif
-#ifdef POB_MESH_FC_INLINE  // (pob_face_consts' operations in the guard's policy)
-  {
-    const float dA = F.ha2 * F.ha2, dB = F.hb2 * F.hb2, e_d = FMA(F.hb2, F.hb2, F.ha2 * F.ha2);
-    const float dd[3] = {dA, dB, e_d};
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float len = g.sqrt(dd[c]);
-      F.cv[POB_FC_IL(c)] = g.rcp(len + 1e-6f);
-      F.cv[POB_FC_HL(c)] = len * 0.5f;
-      F.cv[POB_FC_IDD(c)] = g.rcp(dd[c] + 1e-6f);
-    }
-    F.cv[POB_FC_ED] = e_d;
-    F.cv[POB_FC_IDET(0)] = g.rcp(FMA(dA, e_d, -(dA * dA)));
-    F.cv[POB_FC_IDET(1)] = g.rcp(FMA(e_d, dB, -(dB * dB)));
-  }
-#endif
   (void)g;
   return F;
 }
@@ -432,12 +373,6 @@ POB_D MCand mtri_pick_ties_ool(const int f, const v3 La, const v3 Lb, const floa
   HostGuard g;
   return mtri_pick_ties(g, mface(g, f, mcap_seg(g, La, Lb), hx, hy, hz, fcw), t);
 }
-#elif defined(POB_MESH_TIES_INLINE)  // A/B build switch: the tie path inline
-POB_D MCand mtri_pick_ties_ool(const int f, const v3 La, const v3 Lb, const float hx, const float hy, const float hz,
-                               fcptr_t fcw, const int t) {
-  GuardBranch g;
-  return mtri_pick_ties(g, mface(g, f, mcap_seg(g, La, Lb), hx, hy, hz, fcw), t);
-}
 #else
 __device__ __attribute__((noinline)) MCand mtri_pick_ties_ool(const int f, const v3 La, const v3 Lb, const float hx,
                                                            const float hy, const float hz, fcptr_t fcw,
@@ -547,32 +482,10 @@ POB_D MFaceOut mesh_face_contacts(G &g, const int f, const v3 La, const v3 Lb, c
   }
   return o;
 }
-#ifndef POB_MESH_HOST
-// out of line (GuardBranch only: stateless): the face's working set leaves the caller's
-// register allocation -- the caller saves its live registers around the call, i.e. only when
-// a lane of the wave has a face item (POB_MESH_NOINLINE)
-__device__ __attribute__((noinline)) MFaceOut mesh_face_ool(const int f, const v3 La, const v3 Lb, const float hx,
-                                                         const float hy, const float hz, fcptr_t fcw,
-                                                         const float r, const float T) {
-  GuardBranch g;
-  return mesh_face_contacts(g, f, La, Lb, hx, hy, hz, fcw, r, T);
-}
-#endif
-#ifndef POB_MESH_NOINLINE
-#define POB_MESH_NOINLINE 0
-#endif
 // emit(tau, n_local, dist) for triangle 0 then 1 when it penetrates
 template <class G, class Fn>
 POB_D void mesh_face(G &g, const int f, const v3 La, const v3 Lb, const float hx, const float hy, const float hz,
                      fcptr_t fcw, const float r, const float T, Fn &&emit) {
-#if POB_MESH_NOINLINE && !defined(POB_MESH_HOST)
-  if constexpr (std::is_same<G, GuardBranch>::value) {
-    const MFaceOut o = mesh_face_ool(f, La, Lb, hx, hy, hz, fcw, r, T);
-    if (o.hit[0]) emit(o.tau[0], o.nl[0], o.dist[0]);
-    if (o.hit[1]) emit(o.tau[1], o.nl[1], o.dist[1]);
-    return;
-  }
-#endif
   const MFaceOut o = mesh_face_contacts(g, f, La, Lb, hx, hy, hz, fcw, r, T);
   if (o.hit[0]) emit(o.tau[0], o.nl[0], o.dist[0]);
   if (o.hit[1]) emit(o.tau[1], o.nl[1], o.dist[1]);
@@ -746,11 +659,7 @@ template <int NB, bool LANE_FALLBACK = true, int HAND = 0, class G, class SegOf,
 POB_D void mesh_wave_walk(G &g, const float *WT, fcptr_t FC, const float cz, const float hz, uint64_t (&M)[NB],
                           SegOf &&seg_of, Apply &&apply) {
   if constexpr (LANE_FALLBACK) {
-#ifdef POB_MESH_LANE_WALK
-    if (true) {  // A/B build switch: the per-lane walk everywhere
-#else
     if (__ballot(1) != ~0ull) {
-#endif
       mesh_lane_walk<NB>(g, WT, FC, cz, hz, M, seg_of, apply);
       return;
     }

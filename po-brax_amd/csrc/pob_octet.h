@@ -51,8 +51,8 @@ static_assert(OT_TAB_FLOATS % 4 == 0, "the broadphase boxes after the wall rows 
 
 #define OTV(T, f) V((T)[(f)], (T)[(f) + 1], (T)[(f) + 2])
 // The eight-lane kernel runs at most a few waves per SIMD, so the system table's scalars
-// may stay in SGPRs for the whole substep loop (no per-stage re-load, pob_physics.h
-// launder), and the lane's role row lives in VGPRs (k_step_oct copies it out of LDS).
+// may stay in SGPRs for the whole substep loop (no per-stage re-load, pob_physics.h),
+// and the lane's role row lives in VGPRs (k_step_oct copies it out of LDS).
 #define OLAUNDER(p) (p)
 
 // lane m of an env's octet <-> 7 - m (A_k <-> B_k)
@@ -78,9 +78,7 @@ struct OGround {
 // mesh_wave_walk HAND 2), the position responses then following the list after the walk
 // instead of inside its hand-over.  HH B = 16 384 0.1075 -> 0.0950 ms; TAG B = 12 288 / 16 384
 // +0.8 / +1.7 %, GA +1.3 % (profiles/r7i/ab.txt), so HH only.
-#ifndef POB_OCT_POOL_KINDS
 #define POB_OCT_POOL_KINDS 1
-#endif
 __host__ __device__ constexpr bool oct_pool(int kind) { return kind >= 0 && ((POB_OCT_POOL_KINDS >> kind) & 1) != 0; }
 #define OPOOL_N 64
 struct OMesh {
@@ -223,11 +221,7 @@ POB_D void ocontacts_position(G &g, const HCon &SC, const float *OT, const float
   {
     const float mnx = fminf(b.x[0].x, b.x[1].x), mxx = fmaxf(b.x[0].x, b.x[1].x);
     const float mny = fminf(b.x[0].y, b.x[1].y), mxy = fmaxf(b.x[0].y, b.x[1].y);
-#ifdef POB_EXP_NO_WALLS
-    const int nw = 0;  // timing experiment only
-#else
     const int nw = HW.n_walls;
-#endif
     // the boxes from the LDS table (HW_BOX, after the wall rows) at each collide substep: held
     // in VGPRs across the loop they pushed the two-wave build past 256 registers
     const float *WB = WT + POB_MAXW * POB_WALL_FLOATS + HW_BOX;
@@ -257,9 +251,6 @@ POB_D void ocontacts_position(G &g, const HCon &SC, const float *OT, const float
       }
     }
   }
-#ifdef POB_EXP_NO_WALK
-  return;  // timing experiment only: broadphase and face cull, no face walk
-#endif
   // one position response (slot s, the contact's tau, n, dist)
   auto pos_one = [&](const int s, const float tau, const v3 n, const float dist) {
     const v3 x = vsel3(s == 0, b.x[0], b.x[1]);

@@ -17,26 +17,17 @@ struct Body {
   v3 w[POB_NDYN];
 };
 
-// launder(): with POB_LAUNDER the table pointer is hidden from loop-invariant code motion
-// (each table value's scalar load stays next to its use).  Round 1 needed it against SGPR
-// spills; with the scheduling fences and the current kernels the compiler's own placement
-// measured 0.7-0.9 % faster at B = 65 536 (HH, TAG, ant; no new scratch), so it is off.
+// The table pointer is used as it is.  (A variant tried and removed: the pointer hidden from
+// loop-invariant code motion per stage, so that each table value's scalar load stays next to
+// its use.  Round 1 needed it against SGPR spills; with the scheduling fences and the current
+// kernels the compiler's own placement measured 0.7-0.9 % faster at B = 65 536 -- HH, TAG,
+// ant; no new scratch.)
 typedef __attribute__((address_space(4))) const pob_sys csys_t;  // constant address space
-POB_D csys_t *launder(csys_t *p) {
-#ifdef POB_LAUNDER
-  asm volatile("" : "+s"(p));
-#endif
-  return p;
-}
 // the walls' face constants (pob_sys::face_c, pob_mesh.h MFace)
 POB_D fcptr_t pob_face_table(csys_t &S) { return (fcptr_t)&S.face_c[0][0][0]; }
 // Scheduling fence between the independent joint / contact blocks: without it the machine
 // scheduler interleaves all of them for ILP and the live set blows past 512 registers.
-#ifdef POB_NO_FENCE
-#define POB_FENCE() ((void)0)
-#else
 #define POB_FENCE() __builtin_amdgcn_sched_barrier(0)
-#endif
 
 // Per-lane LDS scratch, lane-minor (element e of lane t at base[e * BS + t]): conflict-free
 // ds_read/ds_write_b32.  Holds what the substep keeps live but rarely touches (the

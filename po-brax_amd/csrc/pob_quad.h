@@ -10,7 +10,7 @@
 // lanes) and leg k: local body 0 = torso, 1 = Aux k+1 (global 2k+1), 2 = lower leg
 // (global 2k+2); local joint 0 = global 2k (torso -> aux), 1 = global 2k+1 (aux -> leg).
 // Leg tables come from an LDS copy of pob_sys::leg (one row per leg); the scalar table
-// (torso and global constants) is laundered per stage (pob_physics.h).
+// (torso and global constants) is read through the constant address space (pob_physics.h).
 // Every body's accumulations run in its owner lane in the oracle's order.  The torso's
 // cross-leg sums (actuator + damping torques of joints 0,2,4,6; the position corrections
 // those joints apply to the torso) are gathered with DPP quad broadcasts, and every lane
@@ -173,28 +173,18 @@ struct QMesh {
 // then) and both passes re-walk every face the cull keeps from them (qwalls_rewalk_inl) -- the
 // same operations on the same operands: the same contacts in the same order.  Nothing of this
 // is live in registers between the passes but the count.
-#ifndef QK
 #define QK 12  // (8: HH B = 65 536 0.2038 ms with the split launch, 12: 0.1634 -- fewer fix-up waves; 16, 24: the same; profiles/r6c_ab.txt)
-#endif
 struct QWalls {
   int nct;                // wall contacts of the position pass
   float c[6 * QK];        // the first QK: body, tau, n, dist (the re-walk builds, OVF)
   float seg[6 * QNB];     // nct > QK only: the segments a, b of the three bodies
   // the block-cooperative walk only: the torso's contact slots [cb[0], cb[1]) and the lane's own
   // Aux and lower-leg slots [cb[2], cb[3]), [cb[3], cb[4]) (bw_quad_ranges; qcb_lo), and per body
-  // the slots that hold a contact (bw_hit_bits, POB_QUAD_HIT_MASK)
+  // the slots that hold a contact (the hit mask, bw_hit_bits)
   int cb[QNB + 2];
   uint32_t hm[QNB];
 };
 POB_D constexpr int qcb_lo(const int l) { return l == 0 ? 0 : l + 1; }  // body l's slots: [cb[qcb_lo(l)], cb[qcb_lo(l) + 1])
-#ifndef POB_QUAD_WAVE_WALK
-#define POB_QUAD_WAVE_WALK 1  // 1: the wave-cooperative face walk (pob_mesh.h mesh_wave_walk)
-#endif
-#if POB_QUAD_WAVE_WALK
-#define QWALK mesh_wave_walk
-#else
-#define QWALK mesh_lane_walk
-#endif
 
 // The Ant's capsules (checked by pob_system.cpp) have opposite end points +-e0 in the body
 // xy-plane, so one rotation rv = rotate(e0, q) serves both (rotate(-e0) = -rv exactly), and a
@@ -216,11 +206,7 @@ POB_D uint32_t qwall_mask(csys_t &S, const QBody &b) {
     mnx = fminf(mnx, b.x[l].x); mxx = fmaxf(mxx, b.x[l].x);
     mny = fminf(mny, b.x[l].y); mxy = fmaxf(mxy, b.x[l].y);
   }
-#ifdef POB_EXP_NO_WALLS
-  const int nw = 0;  // timing experiment only
-#else
   const int nw = S.n_walls;
-#endif
   uint32_t m = 0u;
 #pragma unroll
   for (int w = 0; w < POB_MAXW; ++w) {
@@ -322,27 +308,11 @@ POB_D void qpose_seg(csys_t &S, const float *LT, const QBody &b, const int l, v3
   seg = l != 0;
 }
 
-// The face walk of the detection: the cooperative walk (every lane of the wave is active in
-// the substeps, step_quad_body) or, in the per-lane build (POB_QUAD_WAVE_WALK 0), each lane's
-// own walk out of line (qwalls_walk_ool).  The contacts go to the lane's store.
-template <bool LANE>
+// The face walk of the detection: the wave-cooperative walk (every lane of the wave is active
+// in the substeps, step_quad_body).  The contacts go to the lane's store.
 POB_D void qwalls_walk(csys_t &S, const float *LT, const float *WT, const QBody &b, uint64_t (&M)[QNB], QWalls &ws) {
   GuardBranch g;
-#if POB_QUAD_WAVE_WALK
-  if (!LANE) {
-    mesh_wave_walk<QNB, false>(g, WT, pob_face_table(S), S.wall_cz, S.wall_hz, M,
-               [&](const int l, v3 &A, v3 &B, float &r, bool &seg) { qpose_seg(S, LT, b, l, A, B, r, seg); },
-               [&](const int l, const int, const float tau, const v3 n, const float dist) {
-      if (ws.nct < QK) {
-        float *c = ws.c + 6 * ws.nct;
-        c[0] = (float)l; c[1] = tau; c[2] = n.x; c[3] = n.y; c[4] = n.z; c[5] = dist;
-      }
-      ++ws.nct;
-    });
-    return;
-  }
-#endif
-  mesh_lane_walk<QNB>(g, WT, pob_face_table(S), S.wall_cz, S.wall_hz, M,
+  mesh_wave_walk<QNB, false>(g, WT, pob_face_table(S), S.wall_cz, S.wall_hz, M,
              [&](const int l, v3 &A, v3 &B, float &r, bool &seg) { qpose_seg(S, LT, b, l, A, B, r, seg); },
              [&](const int l, const int, const float tau, const v3 n, const float dist) {
     if (ws.nct < QK) {
@@ -352,31 +322,14 @@ POB_D void qwalls_walk(csys_t &S, const float *LT, const float *WT, const QBody 
     ++ws.nct;
   });
 }
-// (the per-lane build's walk, out of line: POB_QUAD_WAVE_WALK 0)
-__device__ __attribute__((noinline)) int qwalls_walk_ool(csys_t *Sp, const float *LT, const float *WT, v3 x0, v3 x1,
-                                                       v3 x2, q4 q0, q4 q1, q4 q2, uint64_t m0, uint64_t m1,
-                                                       uint64_t m2, QWalls *ws) {
-  csys_t &S = *launder(Sp);
-  QBody b;
-  b.x[0] = x0; b.x[1] = x1; b.x[2] = x2;
-  b.q[0] = q0; b.q[1] = q1; b.q[2] = q2;
-  uint64_t M[QNB] = {m0, m1, m2};
-  ws->nct = 0;
-  qwalls_walk<true>(S, LT, WT, b, M, *ws);
-  return ws->nct;
-}
 
 // The fast launch's walk (OVF false): the contacts go to the wave's LDS pool (QLds) in walk
 // order -- each hand-over step allocates the pool slots of the lanes receiving a contact by
 // ballot / mbcnt, and a lane links its contacts into a list (head in its LDS slot, each entry's
 // last float = body | (next + 1) << 2) -- so the passes read them from LDS instead of a private
 // array in scratch.  A wave whose contacts exceed the pool reports it in ovf (the fix-up launch
-// then steps it with the re-walks).
-// (POB_QUAD_POOL_DIRECT, the default: the winner lanes store the contacts and the owners only
-// link them -- pob_mesh.h mesh_wave_walk HAND 2)
-#ifndef POB_QUAD_POOL_DIRECT
-#define POB_QUAD_POOL_DIRECT 1
-#endif
+// then steps it with the re-walks).  The winner lanes store the contacts and the owners only
+// link them (pob_mesh.h mesh_wave_walk HAND 2).
 struct QPoolSink {
   float *pool;
   float *head;
@@ -406,21 +359,13 @@ struct QPoolSink {
     }
   }
 };
-// (POB_QUAD_WALK_GACC, an A/B switch: the walk's range guards branch-free, GuardAcc -- a lane
-// that saw an operand outside the fast forms' range sends its wave to the fix-up launch, whose
-// exact branch guards give the same bits for every lane that stayed in range.  Measured HH
-// B = 65 536 0.1509 -> 0.1546 ms, TAG ±0 (profiles/r7m/ab.txt): off)
-#ifndef POB_QUAD_WALK_GACC
-#define POB_QUAD_WALK_GACC 0
-#endif
+// (A variant tried and removed: the walk's range guards branch-free, GuardAcc -- a lane that
+// saw an operand outside the fast forms' range sends its wave to the fix-up launch, whose exact
+// branch guards give the same bits for every lane that stayed in range.  Measured HH
+// B = 65 536 0.1509 -> 0.1546 ms, TAG ±0, profiles/r7m/ab.txt.)
 POB_D void qwalls_walk_pool(csys_t &S, const float *LT, const float *WT, const QBody &b, uint64_t (&M)[QNB],
                             QWalls &ws, const QLds &L, bool &ovf) {
-#if POB_QUAD_WALK_GACC
-  GuardAcc g;
-#else
   GuardBranch g;
-#endif
-#if POB_QUAD_POOL_DIRECT
   QPoolSink sink{L.pool(), L.head(), 0, -1, 0, 0};
   mesh_wave_walk<QNB, false, 2>(g, WT, pob_face_table(S), S.wall_cz, S.wall_hz, M,
              [&](const int l, v3 &A, v3 &B, float &r, bool &seg) { qpose_seg(S, LT, b, l, A, B, r, seg); }, sink);
@@ -429,34 +374,6 @@ POB_D void qwalls_walk_pool(csys_t &S, const float *LT, const float *WT, const Q
   // (a wave whose pool overflowed discards the step; its lists are incomplete -- a lane whose
   // first contact fell past the pool never wrote its head -- so the passes start from none)
   if (sink.npool > QPOOL_N) ws.nct = 0;
-#if POB_QUAD_WALK_GACC
-  ovf = ovf | g.bad();
-#endif
-  return;
-#endif
-  float *pool = L.pool();
-  int npool = 0;  // (wave-uniform)
-  int tail = -1, tail_l = 0;
-  mesh_wave_walk<QNB, false, 1>(g, WT, pob_face_table(S), S.wall_cz, S.wall_hz, M,
-             [&](const int l, v3 &A, v3 &B, float &r, bool &seg) { qpose_seg(S, LT, b, l, A, B, r, seg); },
-             [&](const bool want, const int l, const int, const float tau, const v3 n, const float dist) {
-    const uint64_t m = __ballot(want);
-    if (m == 0ull) return;
-    const int idx = npool + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    npool += __popcll(m);
-    if (want) {
-      if (idx < QPOOL_N) {
-        float *c = pool + 6 * idx;
-        c[0] = tau; c[1] = n.x; c[2] = n.y; c[3] = n.z; c[4] = dist; c[5] = __int_as_float(l);
-        if (tail >= 0) pool[6 * tail + 5] = __int_as_float(((idx + 1) << 2) | tail_l);
-        else *L.head() = __int_as_float(idx);
-        tail = idx;
-        tail_l = l;
-      }
-      ++ws.nct;
-    }
-  });
-  ovf = ovf | (npool > QPOOL_N);
 }
 
 // Wall contact detection of a collide substep, at the pose the position pass projects from
@@ -473,7 +390,7 @@ POB_D void qwalls_detect(csys_t *Sp, const float *LT, const float *WT, const QBo
                          bool *ovf = nullptr) {
   ws.nct = 0;
   if (!WALLS) return;
-  csys_t &S = *launder(Sp);
+  csys_t &S = *Sp;
   const v3 rv_leg = qrot_xy(qcap_end(S, LT, 2, 0), b.q[2]);
   uint64_t M[QNB];
   {
@@ -482,44 +399,13 @@ POB_D void qwalls_detect(csys_t *Sp, const float *LT, const float *WT, const QBo
     const uint32_t lw = qwall_mask(S, b);
     qmesh_items(S, LT, WT, lw | (lw << 8) | (lw << 16), ms, M);
   }
-#ifdef POB_EXP_NO_WALK
-  return;  // timing experiment only: broadphase and face cull, no face walk
-#endif
-#ifdef POB_EXP_WALK_DEAD
-  if (S.n_walls < 64) return;  // timing experiment only: the walk compiled in, never run
-#endif
-#ifdef POB_EXP_CULL_ONLY
-  {  // timing experiment only: the cull's items kept alive, no walk, the passes compiled in
-    uint32_t k0 = (uint32_t)M[0], k1 = (uint32_t)M[1], k2 = (uint32_t)M[2];
-    asm volatile("" : "+v"(k0), "+v"(k1), "+v"(k2));
-    int z = (int)((k0 ^ k1 ^ k2) & 0u);
-    asm volatile("" : "+v"(z));
-    ws.nct = z;
-    return;
-  }
-#endif
   if (!__any((M[0] | M[1] | M[2]) != 0ull)) return;
-#if POB_QUAD_WAVE_WALK
   // (the step kernel runs its substeps on all 64 lanes of every wave: step_quad_body)
   if (!OVF) {
     qwalls_walk_pool(S, LT, WT, b, M, ws, L, *ovf);
     return;
   }
-  qwalls_walk<false>(S, LT, WT, b, M, ws);
-#else
-  ws.nct = qwalls_walk_ool(Sp, LT, WT, b.x[0], b.x[1], b.x[2], b.q[0], b.q[1], b.q[2], M[0], M[1], M[2], &ws);
-#endif
-#ifdef POB_EXP_NO_APPLY
-  {  // timing experiment only: the walk runs, its contacts are not applied
-    int z = ws.nct & 0;
-    asm volatile("" : "+v"(z));
-    ws.nct = z;
-  }
-#endif
-  if (!OVF) {
-    *ovf = *ovf | (ws.nct > QK);
-    return;
-  }
+  qwalls_walk(S, LT, WT, b, M, ws);
   if (ws.nct > QK) {  // (rare) the detection-time segments for the re-walks
     QMesh ms;
     qmesh_segments(S, LT, b, rv_leg, ms);
@@ -545,8 +431,8 @@ POB_D void qwalls_detect(csys_t *Sp, const float *LT, const float *WT, const QBo
 // the body a compile-time value needs no selects over the lane's three bodies (DESIGN.md §4
 // "Round-8 findings").  The torso is the same body in the four lanes of a quad: its items are
 // published once, by the quad's lane 0, and its contact slots read by all four; and the owners
-// look for the slots that hold a contact once, after barrier 2, not once in each pass (the
-// switches below; DESIGN.md §4 "Round-9 findings").
+// look for the slots that hold a contact once, after barrier 2, not once in each pass
+// (DESIGN.md §4 "Round-9 findings").
 // Two barriers per collide substep suffice: between barrier 2 and the next barrier 1 a wave
 // reads (apply) and writes (the next publish) only its OWN segment, and the others touch that
 // segment only between a barrier 1 and the barrier 2 after it (evaluation: they read its
@@ -559,23 +445,14 @@ POB_D void qwalls_detect(csys_t *Sp, const float *LT, const float *WT, const QBo
 // executes both barriers whatever its items, its lanes past the batch, its overflow state --
 // a wave past the batch (dead) publishes no items and still evaluates its rounds; an overflow
 // (block-uniform: every wave derives it from the same four counts) only empties the deal.
-// Three A/B switches (DESIGN.md §4 "Round-9 findings"), each 1 = on:
-//   POB_QUAD_TORSO_ONCE    the torso's items counted and published by the quad's lane 0 alone
-//                          (its four lanes hold the same torso) and applied by all four from that
-//                          lane's slots (bw_quad_ranges) -- 0: every lane publishes its replica's;
-//   POB_QUAD_HIT_MASK      one scan of the contact slots per collide substep into a hit mask per
-//                          body that both passes walk (bw_hit_bits) -- 0: each pass skips the
-//                          no-contact slots on its own (qblock_next_hit);
-//   POB_QUAD_PREFIX_SHORT  the prefix's steps 2 .. 6 only in a wave with a lane of 4 items or more.
-#ifndef POB_QUAD_TORSO_ONCE
-#define POB_QUAD_TORSO_ONCE 1
-#endif
-#ifndef POB_QUAD_HIT_MASK
-#define POB_QUAD_HIT_MASK 1
-#endif
-#ifndef POB_QUAD_PREFIX_SHORT
-#define POB_QUAD_PREFIX_SHORT 1
-#endif
+// Three round-9 changes (DESIGN.md §4 "Round-9 findings"; the forms they replaced were build
+// variants, since removed):
+//   * the torso's items counted and published by the quad's lane 0 alone (its four lanes hold
+//     the same torso) and applied by all four from that lane's slots (bw_quad_ranges), not
+//     published by every lane from its replica;
+//   * one scan of the contact slots per collide substep into a hit mask per body that both
+//     passes walk (bw_hit_bits), not a skip over the no-contact slots in each pass;
+//   * the prefix's steps 2 .. 6 only in a wave with a lane of 4 items or more.
 struct QBlock {
   float *xch;  // segment 0 (the block's LDS + QPOOL_OFF; segment w at + w * 64 QL_FLOATS)
   int w;       // the wave's number in the block
@@ -590,7 +467,7 @@ POB_D void qblock_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" :
 
 POB_D void qwalls_detect_block(csys_t *Sp, const float *LT, const float *WT, const QBody &b, QWalls &ws, const QLds &L,
                                QBlock &blk) {
-  csys_t &S = *launder(Sp);
+  csys_t &S = *Sp;
   uint64_t M[QNB];
   QMesh ms;  // (the cull's segments: the publish writes them into the records)
   {
@@ -600,16 +477,9 @@ POB_D void qwalls_detect_block(csys_t *Sp, const float *LT, const float *WT, con
     qmesh_items(S, LT, WT, lw | (lw << 8) | (lw << 16), ms, M);
   }
   if (blk.dead) { M[0] = 0ull; M[1] = 0ull; M[2] = 0ull; }
-#ifdef POB_EXP_NO_WALK
-  // timing experiment only: broadphase, face cull and the barriers, no items.  (This and the two
-  // below change the states: time the first few steps from reset only -- ants that sink into the
-  // walls load the later steps with items, DESIGN.md §4 "Round-8 findings")
-  M[0] = 0ull; M[1] = 0ull; M[2] = 0ull;
-#endif
   // publish: the lanes' items in lane order, each lane's in walk order (slot, then bit) -- body
   // by body with the slot a compile-time value: the record is the cull's segment of that body
   float *own = L.pool();
-#if POB_QUAD_TORSO_ONCE
   {
     // the torso's items once per quad: its mask from the quad's lane 0 (the four replicas' masks
     // are the same set -- a wall outside a lane's broadphase has every torso face culled -- and the
@@ -620,13 +490,9 @@ POB_D void qwalls_detect_block(csys_t *Sp, const float *LT, const float *WT, con
   }
   const int n0 = __builtin_popcountll(M[0]);  // the quad's torso items
   if (!bw_quad_lead(L.t)) M[0] = 0ull;
-#else
-  const int n0 = __builtin_popcountll(M[0]);
-#endif
   const int n1 = __builtin_popcountll(M[1]), n2 = __builtin_popcountll(M[2]);
   const int nl = bw_lane_count(M[0], M[1], M[2]);
   int base = 0, tot = 0;
-#if POB_QUAD_PREFIX_SHORT
 #pragma unroll
   for (int bit = 0; bit < QBW_PREFIX_SHORT_BITS; ++bit) bw_prefix_step(__ballot(((nl >> bit) & 1) != 0), L.t, bit, base, tot);
   if (__any(bw_prefix_needs_all(nl))) {  // (wave-uniform; rare: a lane seldom holds more than 3 items)
@@ -634,14 +500,8 @@ POB_D void qwalls_detect_block(csys_t *Sp, const float *LT, const float *WT, con
     for (int bit = QBW_PREFIX_SHORT_BITS; bit < QBW_PREFIX_BITS; ++bit)
       bw_prefix_step(__ballot(((nl >> bit) & 1) != 0), L.t, bit, base, tot);
   }
-#else
-#pragma unroll
-  for (int bit = 0; bit < QBW_PREFIX_BITS; ++bit) bw_prefix_step(__ballot(((nl >> bit) & 1) != 0), L.t, bit, base, tot);
-#endif
-#if POB_QUAD_HIT_MASK
   // a body past the hit mask's width: the wave publishes an overflowing count (the fix-up launch)
   tot = bw_hit_count(tot, __any((n0 > blk.hitw) | (n1 > blk.hitw) | (n2 > blk.hitw)) != 0);
-#endif
   {
     int at = base;
 #pragma unroll
@@ -680,27 +540,11 @@ POB_D void qwalls_detect_block(csys_t *Sp, const float *LT, const float *WT, con
   }
   qblock_barrier();  // BARRIER 2: every contact slot of the deal is written
   ++blk.sub;
-#if POB_QUAD_TORSO_ONCE
   // (all four lanes apply the torso's contacts from the quad's lane-0 slots: the same words in
   // the same order, so the replicas stay bit-identical)
   const int base0 = __float_as_int(quad_bcast<0>(__int_as_float(base)));
   bw_quad_ranges(L.t, base0, n0, base, n1, n2, d.ovf, ws.cb);
-#else
-  {
-    int c[QNB + 1];
-    bw_body_ranges(base, n0, n1, n2, d.ovf, c);
-    ws.cb[0] = c[0]; ws.cb[1] = c[1]; ws.cb[2] = c[1]; ws.cb[3] = c[2]; ws.cb[4] = c[3];
-  }
-#endif
-#ifdef POB_EXP_NO_APPLY
-  {  // timing experiment only: the walk runs, its contacts are not applied
-    int z = ws.cb[0], y = ws.cb[2];
-    asm volatile("" : "+v"(z), "+v"(y));
-    ws.cb[1] = z; ws.cb[3] = y; ws.cb[4] = y;
-  }
-#endif
   ws.nct = (ws.cb[1] - ws.cb[0]) + (ws.cb[4] - ws.cb[2]);
-#if POB_QUAD_HIT_MASK
   // the one hit scan of the substep: per body, the dist words of its items' two triangles (one
   // ds_read2 per item, the reads independent of each other) into the hit mask both passes walk
 #pragma unroll
@@ -718,21 +562,6 @@ POB_D void qwalls_detect_block(csys_t *Sp, const float *LT, const float *WT, con
     ws.hm[l] = hm;
   }
   ws.nct = (int)(ws.hm[0] | ws.hm[1] | ws.hm[2]);  // (the passes ask only whether it is 0)
-#endif
-}
-
-// The lane's next contact slot in [c, c1) that holds a contact (c1: none left).  The owners
-// skip their no-contact slots on their own, so every iteration of the passes' apply loops
-// carries a contact on each lane that has one left (iterations = the busiest lane's contacts,
-// as with the per-wave walk's lists, not its triangles).
-POB_D int qblock_next_hit(const float *sg, int c, const int c1) {
-#pragma unroll 1
-  while (true) {
-    const bool skip = c < c1 && __float_as_int(sg[bw_con_off(c) + QBW_CON_DW - 1]) == QBW_NO_CONTACT;
-    if (!__any(skip)) break;
-    c = skip ? c + 1 : c;
-  }
-  return c;
 }
 
 // One wall contact applied at the position level (penetration r - dist, the contact at the
@@ -763,50 +592,14 @@ POB_D void qwall_vel_one(G &g, csys_t &S, const HCon &SC, const float *LT, const
   qput3(l, dW, dw);
 }
 
-// The re-walk of a lane whose contacts overflowed the store (rare), out of line so that the
-// walk's registers stay out of the position and velocity passes: every face the cull keeps
+// The re-walk of a lane whose contacts overflowed the store (rare): every face the cull keeps
 // over every wall, from the detection-time segments (the broadphase only skips walls whose
-// faces are all culled), each contact applied in walk order.  State through a private block.
-struct QOvf {
-  v3 x[QNB], px[QNB], v[QNB], w[QNB], a[QNB], b[QNB], d0[QNB], d1[QNB];
-  q4 q[QNB], pq[QNB];
-  float fric;
-  int on;
-};
-template <bool VEL>
-__device__ __attribute__((noinline)) void qwalls_rewalk(csys_t *Sp, const float *LT, const float *WT, QOvf *st) {
-  csys_t &S = *launder(Sp);
-  GuardBranch g;
-  const HCon SC{st->fric, S.inv_h};
-  v3 x[QNB], px[QNB], v[QNB], w[QNB], d0[QNB], d1[QNB];
-  q4 q[QNB], pq[QNB];
-  QMesh ms;
-#pragma unroll
-  for (int l = 0; l < QNB; ++l) {
-    x[l] = st->x[l]; px[l] = st->px[l]; v[l] = st->v[l]; w[l] = st->w[l]; d0[l] = st->d0[l]; d1[l] = st->d1[l];
-    q[l] = st->q[l]; pq[l] = st->pq[l]; ms.a[l] = st->a[l]; ms.b[l] = st->b[l];
-  }
-  const uint32_t wa = st->on ? (1u << S.n_walls) - 1u : 0u;
-  uint64_t M[QNB];
-  qmesh_items(S, LT, WT, wa | (wa << 8) | (wa << 16), ms, M);
-  QWALK<QNB>(g, WT, pob_face_table(S), S.wall_cz, S.wall_hz, M,
-             [&](const int l, v3 &A, v3 &B, float &r, bool &seg) { qmesh_seg(S, LT, ms, l, A, B, r, seg); },
-             [&](const int l, const int, const float tau, const v3 n, const float dist) {
-    if (VEL) qwall_vel_one(g, S, SC, LT, x, q, v, w, l, tau, n, dist, d0, d1);
-    else qwall_pos_one(g, S, SC, LT, x, q, px, pq, l, tau, n, dist, d0, d1);
-  });
-#pragma unroll
-  for (int l = 0; l < QNB; ++l) { st->d0[l] = d0[l]; st->d1[l] = d1[l]; }
-}
-
-// The same re-walk inline (POB_QUAD_REWALK_INLINE, the default): the wave-cooperative walk
+// faces are all culled), each contact applied in walk order.  Inline: the wave-cooperative walk
 // with no lane fallback (the step kernel's substeps run on all 64 lanes) and no call -- a call
 // site in the pass, however rarely taken, confines every value live across it to the
-// callee-saved registers, which spilled the substep's state at every collide substep.  The
-// segments come from the store, the substep-start pose (position pass) from LDS.
-#ifndef POB_QUAD_REWALK_INLINE
-#define POB_QUAD_REWALK_INLINE 1
-#endif
+// callee-saved registers, which spilled the substep's state at every collide substep (the
+// out-of-line form, since removed).  The segments come from the store, the substep-start pose
+// (position pass) from LDS.
 template <bool VEL>
 POB_D void qwalls_rewalk_inl(csys_t &S, const float *LT, const float *WT, const QBody &b, const QLds &L,
                              const QWalls &ws, const bool ovf, const float fric, v3 (&d0)[QNB], v3 (&d1)[QNB]) {
@@ -841,7 +634,7 @@ POB_D void qwalls_rewalk_inl(csys_t &S, const float *LT, const float *WT, const 
 template <bool WALLS, bool OVF = true, bool COOP = false>
 POB_D void qcontacts_position(csys_t *Sp, const float *LT, const float *WT, QBody &b, const QLds &L, QGround &gc,
                               const QWalls &ws, v3 (&DX)[QNB], v3 (&DA)[QNB], const float fric) {
-  csys_t &S = *launder(Sp);
+  csys_t &S = *Sp;
   const HCon SC{fric, S.inv_h};
   GuardBranch g;
   {
@@ -866,13 +659,8 @@ POB_D void qcontacts_position(csys_t *Sp, const float *LT, const float *WT, QBod
     const float *sg = L.pool();
 #pragma unroll
     for (int l = 0; l < QNB; ++l) {
-#if POB_QUAD_HIT_MASK
       uint32_t hm = ws.hm[l];
       if (!__any(hm != 0u)) continue;
-#else
-      const int c1 = ws.cb[qcb_lo(l) + 1];
-      if (!__any(ws.cb[qcb_lo(l)] < c1)) continue;
-#endif
       const v3 px = L.get3(l, QF_PX);
       const q4 pq = L.get4(l, QF_PQ);
       // (the capsule end rotated once per body: qseg_point's operands)
@@ -883,7 +671,6 @@ POB_D void qcontacts_position(csys_t *Sp, const float *LT, const float *WT, QBod
         const v3 pe = l == 0 ? b.x[0] : vfma(rv, tau, b.x[l]);
         owall_position(g, SC, r - dist, pe, V(p[1], p[2], p[3]), 1e-6f + dist, im, b.x[l], b.q[l], pq, px, DX[l], DA[l]);
       };
-#if POB_QUAD_HIT_MASK
       // (the hit mask's set bits, lowest first: the lane's contacts in walk order)
 #pragma unroll 1
       while (__any(hm != 0u)) {
@@ -892,17 +679,6 @@ POB_D void qcontacts_position(csys_t *Sp, const float *LT, const float *WT, QBod
           hm &= hm - 1u;
         }
       }
-#else
-      int c = qblock_next_hit(sg, ws.cb[qcb_lo(l)], c1);
-#pragma unroll 1
-      while (__any(c < c1)) {
-        if (c < c1) {
-          apply(sg + bw_con_off(c));
-          ++c;
-        }
-        c = qblock_next_hit(sg, c, c1);
-      }
-#endif
     }
     return;
   }
@@ -910,7 +686,6 @@ POB_D void qcontacts_position(csys_t *Sp, const float *LT, const float *WT, QBod
   q4 pq[QNB];
 #pragma unroll
   for (int l = 0; l < QNB; ++l) { px[l] = L.get3(l, QF_PX); pq[l] = L.get4(l, QF_PQ); }
-#if POB_QUAD_WAVE_WALK
   if (!OVF) {  // the fast pass: the lane's list in the wave's pool (a wave with an overflow runs the step again)
     const float *pool = L.pool();
     int ci = ws.nct > 0 ? __float_as_int(*L.head()) : -1;
@@ -925,7 +700,6 @@ POB_D void qcontacts_position(csys_t *Sp, const float *LT, const float *WT, QBod
     }
     return;
   }
-#endif
   const bool ovf = ws.nct > QK;
   const int nc = ovf ? 0 : ws.nct;
 #pragma unroll 1
@@ -936,31 +710,7 @@ POB_D void qcontacts_position(csys_t *Sp, const float *LT, const float *WT, QBod
       qwall_pos_one(g, S, SC, LT, b.x, b.q, px, pq, (int)c[0], c[1], V(c[2], c[3], c[4]), c[5], DX, DA);
     }
   }
-  if (!OVF) return;  // (the fast pass: a wave with an overflow runs the step again)
-#if POB_QUAD_REWALK_INLINE
-#ifndef POB_EXP_NO_REWALK
-  if (__any(ovf)) qwalls_rewalk_inl<false>(S, LT, WT, b, L, ws, ovf, fric, DX, DA);  // (timing experiment: off)
-#endif
-  if (false) {
-#else
-  if (__any(ovf)) {
-#endif
-    QOvf st;
-#pragma unroll
-    for (int l = 0; l < QNB; ++l) {
-      st.x[l] = b.x[l]; st.q[l] = b.q[l]; st.px[l] = px[l]; st.pq[l] = pq[l]; st.d0[l] = DX[l]; st.d1[l] = DA[l];
-      st.a[l] = V(ws.seg[6 * l], ws.seg[6 * l + 1], ws.seg[6 * l + 2]);
-      st.b[l] = V(ws.seg[6 * l + 3], ws.seg[6 * l + 4], ws.seg[6 * l + 5]);
-    }
-    st.fric = fric;
-    st.on = ovf ? 1 : 0;
-    qwalls_rewalk<false>(Sp, LT, WT, &st);
-    // everything live after the call comes back from the block (the callee leaves the pose as
-    // it is), so nothing of the pass is live across the call: the call's clobbers then cost no
-    // spills of the substep's state (they would fall in every substep, not only on overflow)
-#pragma unroll
-    for (int l = 0; l < QNB; ++l) { DX[l] = st.d0[l]; DA[l] = st.d1[l]; b.x[l] = st.x[l]; b.q[l] = st.q[l]; }
-  }
+  if (__any(ovf)) qwalls_rewalk_inl<false>(S, LT, WT, b, L, ws, ovf, fric, DX, DA);
 }
 
 // Velocity pass: ground contacts, then the wall contacts from the store (contact points
@@ -968,7 +718,7 @@ POB_D void qcontacts_position(csys_t *Sp, const float *LT, const float *WT, QBod
 template <bool WALLS, bool OVF = true, bool COOP = false>
 POB_D void qcontacts_velocity(csys_t *Sp, const float *LT, const float *WT, QBody &b, const QGround &gc,
                               const QWalls &ws, const QLds &L, v3 (&dV)[QNB], v3 (&dW)[QNB], const float fric) {
-  csys_t &S = *launder(Sp);
+  csys_t &S = *Sp;
   const HCon SC{fric, S.inv_h};
   GuardBranch g;
 #pragma unroll
@@ -983,21 +733,13 @@ POB_D void qcontacts_velocity(csys_t *Sp, const float *LT, const float *WT, QBod
     }
   }
   if (!WALLS || !__any(ws.nct != 0)) return;
-#ifdef POB_EXP_NO_VWALK
-  return;  // timing experiment only: no velocity-pass wall contacts
-#endif
   POB_FENCE();
   if constexpr (COOP) {
     const float *sg = L.pool();  // (body by body, as the position pass)
 #pragma unroll
     for (int l = 0; l < QNB; ++l) {
-#if POB_QUAD_HIT_MASK
       uint32_t hm = ws.hm[l];
       if (!__any(hm != 0u)) continue;
-#else
-      const int c1 = ws.cb[qcb_lo(l) + 1];
-      if (!__any(ws.cb[qcb_lo(l)] < c1)) continue;
-#endif
       const v3 rv = l == 0 ? V(0.0f, 0.0f, 0.0f) : qrot_xy(qcap_end(S, LT, l, 0), b.q[l]);
       const float r = q_cap_r(S, LT, l), im = q_inv_mass(S, LT, l);
       const auto apply = [&](const float *p) {
@@ -1006,7 +748,6 @@ POB_D void qcontacts_velocity(csys_t *Sp, const float *LT, const float *WT, QBod
         ocontact_vel_pe(g, SC, false, r - dist, pe, V(p[1], p[2], p[3]), 1e-6f + dist, im, b.x[l], b.v[l], b.w[l], dV[l],
                         dW[l]);
       };
-#if POB_QUAD_HIT_MASK
 #pragma unroll 1
       while (__any(hm != 0u)) {
         if (hm != 0u) {
@@ -1014,21 +755,9 @@ POB_D void qcontacts_velocity(csys_t *Sp, const float *LT, const float *WT, QBod
           hm &= hm - 1u;
         }
       }
-#else
-      int c = qblock_next_hit(sg, ws.cb[qcb_lo(l)], c1);
-#pragma unroll 1
-      while (__any(c < c1)) {
-        if (c < c1) {
-          apply(sg + bw_con_off(c));
-          ++c;
-        }
-        c = qblock_next_hit(sg, c, c1);
-      }
-#endif
     }
     return;
   }
-#if POB_QUAD_WAVE_WALK
   if (!OVF) {
     const float *pool = L.pool();
     int ci = ws.nct > 0 ? __float_as_int(*L.head()) : -1;
@@ -1043,7 +772,6 @@ POB_D void qcontacts_velocity(csys_t *Sp, const float *LT, const float *WT, QBod
     }
     return;
   }
-#endif
   const bool ovf = ws.nct > QK;
   const int nc = ovf ? 0 : ws.nct;
 #pragma unroll 1
@@ -1054,31 +782,7 @@ POB_D void qcontacts_velocity(csys_t *Sp, const float *LT, const float *WT, QBod
       qwall_vel_one(g, S, SC, LT, b.x, b.q, b.v, b.w, (int)c[0], c[1], V(c[2], c[3], c[4]), c[5], dV, dW);
     }
   }
-  if (!OVF) return;  // (the fast pass: a wave with an overflow runs the step again)
-#if POB_QUAD_REWALK_INLINE
-#ifndef POB_EXP_NO_REWALK
   if (__any(ovf)) qwalls_rewalk_inl<true>(S, LT, WT, b, QLds{nullptr, 0}, ws, ovf, fric, dV, dW);
-#endif
-  if (false) {
-#else
-  if (__any(ovf)) {
-#endif
-    QOvf st;
-#pragma unroll
-    for (int l = 0; l < QNB; ++l) {
-      st.x[l] = b.x[l]; st.q[l] = b.q[l]; st.v[l] = b.v[l]; st.w[l] = b.w[l]; st.d0[l] = dV[l]; st.d1[l] = dW[l];
-      st.a[l] = V(ws.seg[6 * l], ws.seg[6 * l + 1], ws.seg[6 * l + 2]);
-      st.b[l] = V(ws.seg[6 * l + 3], ws.seg[6 * l + 4], ws.seg[6 * l + 5]);
-    }
-    st.fric = fric;
-    st.on = ovf ? 1 : 0;
-    qwalls_rewalk<true>(Sp, LT, WT, &st);
-#pragma unroll
-    for (int l = 0; l < QNB; ++l) {
-      dV[l] = st.d0[l]; dW[l] = st.d1[l];
-      b.x[l] = st.x[l]; b.q[l] = st.q[l]; b.v[l] = st.v[l]; b.w[l] = st.w[l];
-    }
-  }
 }
 
 // sys.info(qp).contact and the legacy collisions: detection and the velocity-level response
@@ -1086,7 +790,7 @@ POB_D void qcontacts_velocity(csys_t *Sp, const float *LT, const float *WT, QBod
 template <bool WALLS, bool LEGACY>
 POB_D void qcontacts_static(csys_t *Sp, const float *LT, const float *WT, const QBody &b, v3 (&dV)[QNB],
                             v3 (&dW)[QNB], const float fric) {
-  csys_t &S = *launder(Sp);
+  csys_t &S = *Sp;
   const HCon SC{fric, S.inv_h};
   GuardBranch g;
   const v3 rv_leg = qrot_xy(qcap_end(S, LT, 2, 0), b.q[2]);
@@ -1143,7 +847,7 @@ struct QTorso {
 // joints_position); for the hip (jl = 0) the torso terms go to *tt
 POB_D void qjoint_position(csys_t *Sp, const float *LT, const QBody &b, const int jl, v3 (&DX)[QNB], v3 (&DA)[QNB],
                            QTorso *tt) {
-  csys_t &S = *launder(Sp);
+  csys_t &S = *Sp;
   const int p = jparent(jl), c = jchild(jl);
   const float imp = q_inv_mass(S, LT, p);
   const float imc = q_inv_mass(S, LT, c);
@@ -1176,11 +880,9 @@ POB_D void qjoint_position(csys_t *Sp, const float *LT, const QBody &b, const in
   const v3 Pa = vscl(vcross(ap, ac), S.half_s_ang);
   const v3 Pl = vscl(ap, dl * S.half_s_ang);
   const v3 s = vadd(Pa, Pl);
-#ifndef POB_EXP_JOINT_ILP
   POB_FENCE();
-#endif
   // point-to-point
-  csys_t &S2 = *launder(Sp);
+  csys_t &S2 = *Sp;
   // (oracle joints_position: P = d k, r x P = (r x d) k with k = s_pos L^2 / (L^2 (imp + imc)
   // + |rp x d|^2 + |rc x d|^2); all zero when the anchors coincide)
   v3 d = vsub(vadd(b.x[c], rc), vadd(b.x[p], rp));
@@ -1208,18 +910,13 @@ POB_D void qtorso_add(v3 &dx, v3 &da, const QTorso &t, const float imp0) {
   da = vadd(da, quad_bcast3<J>(t.t));
 }
 
-// The friction coefficient for the substep loop (POB_QFRIC_REG, default on): read once and
+// The friction coefficient for the substep loop: read once and
 // passed through an empty asm, so the compiler holds it in a register instead of
 // re-issuing a scalar load of pob_sys::friction at each of the ten contact sites of every
 // collide substep (and waiting for it).
-#ifndef POB_QFRIC_REG
-#define POB_QFRIC_REG 1
-#endif
 POB_D float quad_friction(const csys_t &S) {
   float f = S.friction;
-#if POB_QFRIC_REG
   asm volatile("" : "+s"(f));
-#endif
   return f;
 }
 
@@ -1255,7 +952,7 @@ POB_D void qpbd_substep(csys_t *Sp, const float *LT, const float *WT, QBody &b, 
     }
     dw[1] = vsub(vadd(V(0.0f, 0.0f, 0.0f), tt[0]), tt[1]);
     dw[2] = vadd(V(0.0f, 0.0f, 0.0f), tt[1]);
-    csys_t &S = *launder(Sp);
+    csys_t &S = *Sp;
 #pragma unroll
     for (int l = 0; l < QNB; ++l) {
       const v3 v = b.v[l], w = b.w[l];
@@ -1281,7 +978,7 @@ POB_D void qpbd_substep(csys_t *Sp, const float *LT, const float *WT, QBody &b, 
     // (COLLIDE is block-uniform -- the substep's parity -- so the block's waves agree on the barriers)
     if (COLLIDE) qwalls_detect_block(Sp, LT, WT, b, ws, L, *blk);
   } else if (COLLIDE) qwalls_detect<WALLS, OVF>(Sp, LT, WT, b, ws, L, ovf);
-  if (CHECK && COLLIDE) *near = *near | (qwall_mask(*launder(Sp), b) != 0u);
+  if (CHECK && COLLIDE) *near = *near | (qwall_mask(*Sp, b) != 0u);
   // 3. position projection
   QGround gc;
   {
@@ -1291,20 +988,13 @@ POB_D void qpbd_substep(csys_t *Sp, const float *LT, const float *WT, QBody &b, 
     for (int l = 0; l < QNB; ++l) { DX[l] = V(0.0f, 0.0f, 0.0f); DA[l] = V(0.0f, 0.0f, 0.0f); }
     QTorso tq;
     POB_FENCE();
-#ifdef POB_EXP_NO_JOINTS
-    tq.P = V(0.0f, 0.0f, 0.0f);  // timing experiment only
-    tq.t = tq.P;
-#else
     qjoint_position(Sp, LT, b, 0, DX, DA, &tq);
-#ifndef POB_EXP_JOINT_ILP
     POB_FENCE();
-#endif
     qjoint_position(Sp, LT, b, 1, DX, DA, nullptr);
-#endif
     POB_FENCE();
     // torso: global joints 0, 2, 4, 6 (quad lanes 0..3) in order
     {
-      const float imp0 = launder(Sp)->inv_mass[0];
+      const float imp0 = Sp->inv_mass[0];
       qtorso_add<0>(DX[0], DA[0], tq, imp0);
       qtorso_add<1>(DX[0], DA[0], tq, imp0);
       qtorso_add<2>(DX[0], DA[0], tq, imp0);
@@ -1320,7 +1010,7 @@ POB_D void qpbd_substep(csys_t *Sp, const float *LT, const float *WT, QBody &b, 
   // 4. velocity projection
 #pragma unroll
   for (int l = 0; l < QNB; ++l) {
-    csys_t &S = *launder(Sp);
+    csys_t &S = *Sp;
     b.q[l] = qnormalize(b.q[l]);
     b.v[l] = vscl(vsub(b.x[l], L.get3(l, QF_PX)), S.inv_h);
     q4 dq = qmul(b.q[l], qinv(L.get4(l, QF_PQ)));
@@ -1344,7 +1034,7 @@ POB_D void qpbd_substep(csys_t *Sp, const float *LT, const float *WT, QBody &b, 
   }
 }
 
-// The slow wall pass's substep out of line (POB_QUAD_SLOW_OOL): the step's state through a
+// The slow wall pass's substep out of line: the step's state through a
 // private block, so the substep loop of the fast pass carries neither the re-walks' code nor
 // a call's register constraints (a wave runs the slow pass only after a contact-store overflow)
 struct QSlow {
@@ -1407,7 +1097,7 @@ POB_D void qlegacy_substep(csys_t *Sp, const float *LT, const float *WT, QBody &
                            const QLds &L) {
   // kinetic
   {
-    csys_t &S = *launder(Sp);
+    csys_t &S = *Sp;
 #pragma unroll
     for (int l = 0; l < QNB; ++l) {
       b.x[l] = vfma(b.v[l], S.h, b.x[l]);
@@ -1421,7 +1111,7 @@ POB_D void qlegacy_substep(csys_t *Sp, const float *LT, const float *WT, QBody &
   // joints + actuators (accelerations), summed per body in joint order
   v3 dv[QNB], dw[QNB];
   {
-    csys_t &S = *launder(Sp);
+    csys_t &S = *Sp;
     const QSpring hip = qlegacy_joint(S, LT, b, 0, act[0]);
     const QSpring knee = qlegacy_joint(S, LT, b, 1, act[1]);
     const float im0 = S.inv_mass[0], im1 = q_inv_mass(S, LT, 1), im2 = q_inv_mass(S, LT, 2);
@@ -1450,7 +1140,7 @@ POB_D void qlegacy_substep(csys_t *Sp, const float *LT, const float *WT, QBody &
   v3 dV[QNB], dW[QNB];
 #pragma unroll
   for (int l = 0; l < QNB; ++l) { dV[l] = V(0.0f, 0.0f, 0.0f); dW[l] = V(0.0f, 0.0f, 0.0f); }
-  qcontacts_static<WALLS, true>(Sp, LT, WT, b, dV, dW, launder(Sp)->friction);
+  qcontacts_static<WALLS, true>(Sp, LT, WT, b, dV, dW, Sp->friction);
 #pragma unroll
   for (int l = 0; l < QNB; ++l) {
     b.v[l] = vadd(b.v[l], dV[l]); b.w[l] = vadd(b.w[l], dW[l]);

@@ -106,7 +106,7 @@ def wave_rounds(slots):  # (64, 3) item counts of a wave's lanes in a substep ->
     return rounds
 if Bn % 64 == 0:
     now_w, now_b, pool_w, pool_b, blk_items, wav_items = [], [], [], [], [], []
-    once_b, once_w, once_items = [], [], []  # the torso's items once per quad (POB_QUAD_TORSO_ONCE)
+    once_b, once_w, once_items = [], [], []  # the torso's items once per quad (pob_quad.h qwalls_detect_block)
     for t in range(S):
         ls = lane_slots(rec[t]).reshape(Bn // 16, 64, NS, 3)  # (waves, lanes, NSUB, 3)
         wi = ls.sum((1, 3))  # (waves, NSUB) items per wave and substep

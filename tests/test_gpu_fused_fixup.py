@@ -1,7 +1,7 @@
 """GPU: the four-lane step kernel's fix-up inside the fast pass (pob_kernels.hip quad_fixup: a block
 of the block-cooperative kernels whose wall-contact store overflows writes its marks and then
 steps again, from the step's inputs, in the same launch; the per-wave kernels keep the fix-up
-launch, and POB_QUAD_FUSE_WAVE=1 builds them with the call too).  The sixteen- and eight-lane
+launch: with the call in them their fast loops spilled, a build variant since removed).  The sixteen- and eight-lane
 kernels are switched off, so the four-lane kernel runs at these batches; T = 4 steps.
 
 * HH in 256-thread blocks (the block-cooperative walk: a block overflows as a whole and its live

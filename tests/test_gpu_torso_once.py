@@ -1,8 +1,8 @@
 """GPU: the torso's items once per lane quad in the four-lane kernel's block-cooperative wall walk
-(pob_quad.h qwalls_detect_block, POB_QUAD_TORSO_ONCE: the four lanes of an env hold the same
+(pob_quad.h qwalls_detect_block: the four lanes of an env hold the same
 torso, so only quad lane 0 counts and publishes the torso's face items and all four lanes apply
 the torso's contacts from that lane's slots, pob_blockwalk.h bw_quad_ranges), and the one hit
-scan per collide substep (POB_QUAD_HIT_MASK: a 32-bit hit mask per body, a body past its width
+scan per collide substep (bw_hit_bits: a 32-bit hit mask per body, a body past its width
 sends the block to the fix-up launch), bit-exact against the oracle on every field.  The
 sixteen- and eight-lane kernels are switched off, so the four-lane kernel runs at batches just
 above 4 096, in 256-thread blocks, for T = 4 steps.
