@@ -377,6 +377,25 @@ int pob_gru_sequence_backward(const pob_gru *g, int T, long long M, long long B,
                               const float *dy, const float *dh_last /* may be NULL */, float *dtheta,
                               float *dh0 /* may be NULL */, void *workspace, void *stream);
 
+/* ---- Recurrent window, inference only (ABI v8, additive): a pob_gru over S steps of trajectory
+ * arrays in ONE launch that stores nothing but its outputs (the recurrent critic's pass: DESIGN.md
+ * "Recurrent critic"); gru_sequence_forward_ref of csrc/pob_mlp.h bit for bit.  obs (S, B, D), reset
+ * (S, B; may be NULL), idx, h0 (B, H) and norm as for pob_gru_sequence_forward_train; y (S, M, out)
+ * equals S chained pob_gru_forward_norm calls on the gathered rows (so forward_train's y too).
+ * h_first (M, H; may be NULL) receives the state step 0 started from, after step 0's reset (what
+ * h_in_copy is to pob_gru_forward); h_out (M, H; may be NULL) the state after h_out_step steps
+ * (1 <= h_out_step <= S, checked also when h_out is NULL), before step h_out_step's reset.  Without
+ * idx h_out may be h0 itself: a tile reads its rows of h0 before it writes them; with idx it must not
+ * overlap h0, and y and h_first never overlap an input.  Rows >= M are never written.  The limits
+ * are forward_train's.  Arguments are checked before any HIP call; no allocation, no atomics, no
+ * synchronisation: capturable. */
+int pob_gru_sequence_forward(const pob_gru *g, int S, long long M, long long B, const float *obs,
+                             const int32_t *idx /* may be NULL */, const float *h0,
+                             const float *reset /* (S, B), may be NULL */, const float *theta,
+                             float *y /* (S, M, out) */, float *h_first /* (M, H), may be NULL */,
+                             float *h_out /* (M, H), may be NULL */, int h_out_step,
+                             const float *norm /* may be NULL */, float norm_clip, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,10 +2,10 @@
 // (pob_mlp.hip: k_mlp_forward, k_policy_act, the recurrent k_gru_forward, k_gru_policy_act, the
 // observation normaliser's k_obsnorm_*, k_gae, k_ppo_* and the training forward / backward pass
 // k_mlp_forward_train, k_mlp_bwd_*, and the recurrent window's k_gru_seq_forward, k_gru_seq_backward,
-// k_gru_bwd_weights).
+// k_gru_bwd_weights, k_gru_seq_infer).
 // Compiled for the device by hipcc and, with POB_MLP_HOST, for the host by g++
 // (tests/host/mlp_host.cpp, gru_host.cpp, obsnorm_host.cpp, gae_host.cpp, ppo_host.cpp,
-// mlp_bwd_host.cpp, gru_bwd_host.cpp); both with -ffp-contract=off.
+// mlp_bwd_host.cpp, gru_bwd_host.cpp, gru_seq_infer_host.cpp); both with -ffp-contract=off.
 //
 // Every function is a fixed sequence of float32 +, *, fmaf, integer bit operations, and the
 // correctly rounded reciprocal and square root (pob_rcp / pob_sqrt of pob_math.h on the device,
@@ -836,6 +836,40 @@ static inline void gru_sequence_forward_train_ref(const int n_pre, const int *pr
     if (h_last)
       for (int k = 0; k < H; ++k) h_last[m * H + k] = h[k];
   }
+}
+
+// The window without the training arrays (k_gru_seq_infer; DESIGN.md "Recurrent critic"): S chained
+// gru_forward_ref steps on the gathered, normalised rows.  obs (S, B, D), reset (S, B; may be
+// NULL), idx, h0 (B, H), norm as above; y (S, M, out).  h_first (M, H; may be NULL): the state step 0
+// started from, after step 0's reset (the step's h_in_copy).  h_out (M, H; may be NULL): the state
+// after h_out_step steps (1 .. S), before step h_out_step's reset; without idx it may be h0 itself
+// (h0 is read out before anything is written).  Returns 0, or -1 when its buffers cannot be allocated.
+static inline int gru_sequence_forward_ref(const int n_pre, const int *pre_sizes, const int H, const int n_post,
+                                           const int *post_sizes, const int activation, const int S, const long long M,
+                                           const long long B, const float *obs, const int32_t *idx, const float *h0,
+                                           const float *reset, const float *norm, const float norm_clip,
+                                           const float *theta, float *y, float *h_first, float *h_out,
+                                           const int h_out_step) {
+  const int D = pre_sizes[0], out_w = post_sizes[n_post - 1];
+  float *x = (float *)malloc(sizeof(float) * M * D), *rs = (float *)malloc(sizeof(float) * M);
+  float *h = (float *)malloc(sizeof(float) * M * H);
+  if (!x || !rs || !h) { free(x); free(rs); free(h); return -1; }
+  for (long long m = 0; m < M; ++m)
+    for (int k = 0; k < H; ++k) h[m * H + k] = h0[(idx ? idx[m] : m) * H + k];
+  for (int s = 0; s < S; ++s) {
+    for (long long m = 0; m < M; ++m) {
+      const long long b = idx ? idx[m] : m;
+      for (int k = 0; k < D; ++k) x[m * D + k] = obs[((long long)s * B + b) * D + k];
+      rs[m] = reset ? reset[(long long)s * B + b] : 0.0f;
+    }
+    obsnorm_apply_ref(x, M, D, norm, norm_clip);
+    gru_forward_ref(n_pre, pre_sizes, H, n_post, post_sizes, activation, (int)M, x, theta, rs, h, y + (long long)s * M * out_w,
+                    h, s == 0 ? h_first : NULL);
+    if (h_out && s + 1 == h_out_step)
+      for (long long i = 0; i < M * H; ++i) h_out[i] = h[i];
+  }
+  free(x); free(rs); free(h);
+  return 0;
 }
 
 // dtheta (gru_param_count floats, theta's packing: every block an (in + 1, out) matrix whose last

@@ -6,6 +6,7 @@
 //   k_gru_forward, k_gru_policy_act   the recurrent actor (pre-MLP, GRU cell, post-MLP; below)
 //   k_mlp_forward_train, k_mlp_bwd_*  the training forward and the backward pass
 //   k_gru_seq_forward, k_gru_seq_backward, k_gru_bwd_weights   the recurrent window's (at the end)
+//   k_gru_seq_infer    the recurrent window for inference (the recurrent critic's pass)
 //
 // One 64-lane block (one wave) owns a tile of 32 batch rows.  It computes Y^T = W^T X^T with
 // v_mfma_f32_32x32x2_f32: the env is the C column (lane & 31), the A operand of k-step s is row
@@ -1545,6 +1546,75 @@ __global__ __launch_bounds__(64) void k_gru_seq_forward(const GruDesc d, const G
   }
 }
 
+// The window for inference (gru_sequence_forward_ref; DESIGN.md "Recurrent critic"): the tile and
+// the step loop of k_gru_seq_forward with gru_tile_forward's own walk per step (activations fused
+// into the layers, gru_cell), h staying in LDS, and no store but y, h_first and h_out.  The pool is
+// gru_tile_forward's: C = [x ; h], N, P0, P1 -- no gate image.  h_out may be h0 when idx is NULL:
+// the tile's rows of h0 are in LDS before the first barrier, its h_out store comes after it.
+// The pool admits 12 / 7 / 5 / 3 / 2 / 1 blocks a CU; the cell's four accumulators and operand
+// staging take more than 256 registers a lane, so one wave a SIMD (four blocks a CU) is resident.
+// Asking for two waves a SIMD spills to scratch and measured 1.3 - 1.4 x slower.
+template <int R, bool NORM>
+__global__ __launch_bounds__(64) void k_gru_seq_infer(const GruDesc d, const int S, const int M, const long long B,
+                                                      const float *obs, const int32_t *idx, const float *h0,
+                                                      const float *reset, const float *theta, float *y, float *h_first,
+                                                      float *h_out, const int h_out_step, const float *norm,
+                                                      const float clip) {
+  __shared__ float pool[R * MLP_PITCH];
+  const int lane = threadIdx.x, m0 = blockIdx.x * MLP_ROWS;
+  const int valid = M - m0 < MLP_ROWS ? M - m0 : MLP_ROWS;
+  const int D = d.pre[0], I = d.pre[d.n_pre], H = d.hid, out_w = d.post[d.n_post - 1];
+  float *C = pool, *N = C + (I + H) * MLP_PITCH;
+  float *P0 = N + H * MLP_PITCH, *P1 = P0 + d.p_rows[0] * MLP_PITCH;
+  float *Hc = C + I * MLP_PITCH;
+  gru_seq_tile_gather<false>(Hc, h0, H, idx, m0, valid, nullptr, 0.0f, lane);
+  for (int s = 0; s < S; ++s) {
+    __syncthreads();
+    gru_seq_tile_gather<NORM>(d.n_pre ? P0 : C, obs + (size_t)s * B * D, D, idx, m0, valid, norm, clip, lane);
+    if (reset) {
+      const int row = lane & 31, rr = row < valid ? row : valid - 1;
+      const size_t env = idx ? (size_t)idx[m0 + rr] : (size_t)(m0 + rr);
+      const bool zero = reset[(size_t)s * B + env] != 0.0f;
+      if (zero)
+        for (int f = lane >> 5; f < H; f += 2) Hc[f * MLP_PITCH + row] = 0.0f;
+    }
+    __syncthreads();
+    if (h_first && s == 0) mlp_tile_store(h_first, C, I, H, m0, valid, lane);
+    const float *W = theta;
+    float *src = P0;
+    int pp = d.n_pre ? 1 : 0;
+    for (int l = 0; l < d.n_pre; ++l) {
+      const int in = d.pre[l], out = d.pre[l + 1];
+      const float *bias = W + (size_t)in * out;
+      float *dst = l == d.n_pre - 1 ? C : (pp ? P1 : P0);
+      mlp_layer(src, dst, W, bias, in, out, true, d.act, lane);
+      __syncthreads();
+      W = bias + out;
+      src = dst;
+      pp ^= 1;
+    }
+    gru_cell(C, N, W, I, H, lane);
+    __syncthreads();
+    W += (size_t)3 * H * I + (size_t)3 * H * H + 4 * H;
+    if (h_out && s + 1 == h_out_step) mlp_tile_store(h_out, N, 0, H, m0, valid, lane);
+    src = N;
+    int in = H;
+    for (int l = 0; l < d.n_post; ++l) {
+      const int out = d.post[l];
+      const float *bias = W + (size_t)in * out;
+      float *dst = pp ? P1 : P0;
+      mlp_layer(src, dst, W, bias, in, out, l != d.n_post - 1, d.act, lane);
+      __syncthreads();
+      W = bias + out;
+      src = dst;
+      in = out;
+      pp ^= 1;
+    }
+    mlp_tile_store(y + (size_t)s * M * out_w, src, 0, out_w, m0, valid, lane);
+    for (int e = lane; e < MLP_ROWS * H; e += 64) Hc[mlp_img_at(e)] = N[mlp_img_at(e)];  // h' is the next step's h
+  }
+}
+
 // One tile's chain of a transposed product: acc += sum over the `out` features of src of
 // W[row][k] src[k][env] in the order of mlp_kfeat (W's rows are ldw floats apart; rok: this lane's
 // row exists).  mlp_layer_back's inner loop, so that two matrices can share one accumulator.
@@ -1932,6 +2002,34 @@ int pob_gru_sequence_backward(const pob_gru *g, int T, long long M, long long B,
   hipLaunchKernelGGL(k_mlp_bwd_reduce, dim3((unsigned)((g->n_params + 255) / 256)), dim3(256), 0, st,
                      (const double *)partials, n_chunks, g->n_params, dtheta);
   return mlp_hip_check(hipGetLastError(), "k_gru_seq_backward launch");
+}
+
+// k_gru_seq_infer's pool heights, each the tallest that keeps its count of blocks on a CU's 160 KiB
+// of LDS at 132 B a row (12 / 7 / 5 / 3 / 2 / 1 blocks; DESIGN.md "Recurrent critic" has the table)
+#define GRU_SEQ_INFER_N(N, rows, ...)                                                                         \
+  if (rows <= 96) hipLaunchKernelGGL((k_gru_seq_infer<96, N>), grid, dim3(64), 0, st, __VA_ARGS__);           \
+  else if (rows <= 160) hipLaunchKernelGGL((k_gru_seq_infer<160, N>), grid, dim3(64), 0, st, __VA_ARGS__);    \
+  else if (rows <= 248) hipLaunchKernelGGL((k_gru_seq_infer<248, N>), grid, dim3(64), 0, st, __VA_ARGS__);    \
+  else if (rows <= 408) hipLaunchKernelGGL((k_gru_seq_infer<408, N>), grid, dim3(64), 0, st, __VA_ARGS__);    \
+  else if (rows <= 616) hipLaunchKernelGGL((k_gru_seq_infer<616, N>), grid, dim3(64), 0, st, __VA_ARGS__);    \
+  else hipLaunchKernelGGL((k_gru_seq_infer<896, N>), grid, dim3(64), 0, st, __VA_ARGS__);
+
+int pob_gru_sequence_forward(const pob_gru *g, int S, long long M, long long B, const float *obs, const int32_t *idx,
+                             const float *h0, const float *reset, const float *theta, float *y, float *h_first,
+                             float *h_out, int h_out_step, const float *norm, float norm_clip, void *stream) {
+  const int rc = gru_seq_check(g, S, M, B, idx != nullptr, nullptr);
+  if (rc != POB_OK) return rc;
+  if (!obs || !h0 || !theta || !y) return pob_fail_msg(POB_EINVAL, "gru sequence: NULL argument (obs, h0, theta, y)");
+  if (h_out_step < 1 || h_out_step > S)
+    return pob_fail_msg(POB_EINVAL, "gru sequence: h_out_step must be in 1 .. S");
+  GruDesc d = g->d;
+  gru_plan(d, false, d.p_rows);
+  const int rows = d.pre[d.n_pre] + 2 * d.hid + d.p_rows[0] + d.p_rows[1];
+  const dim3 grid((unsigned)((M + MLP_ROWS - 1) / MLP_ROWS));
+  hipStream_t st = (hipStream_t)stream;
+  if (norm) { GRU_SEQ_INFER_N(true, rows, d, S, (int)M, B, obs, idx, h0, reset, theta, y, h_first, h_out, h_out_step, norm, norm_clip) }
+  else { GRU_SEQ_INFER_N(false, rows, d, S, (int)M, B, obs, idx, h0, reset, theta, y, h_first, h_out, h_out_step, norm, norm_clip) }
+  return mlp_hip_check(hipGetLastError(), "k_gru_seq_infer launch");
 }
 
 }  // extern "C"

@@ -67,7 +67,7 @@ EXPORTS = (
     "pob_ppo_loss_workspace_bytes", "pob_ppo_loss",
     "pob_mlp_saved_bytes", "pob_mlp_forward_train", "pob_mlp_backward_workspace_bytes", "pob_mlp_backward",
     "pob_gru_sequence_saved_bytes", "pob_gru_sequence_forward_train", "pob_gru_sequence_backward_workspace_bytes",
-    "pob_gru_sequence_backward",
+    "pob_gru_sequence_backward", "pob_gru_sequence_forward",
 )
 
 
@@ -149,6 +149,9 @@ def _load():
     # gru, T, M, B, idx, reset, theta, saved, dy, dh_last, dtheta, dh0, workspace, stream
     lib.pob_gru_sequence_backward.argtypes = [_VP, C.c_int, C.c_longlong, C.c_longlong, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                               _VP, _VP, _VP]
+    # gru, S, M, B, obs, idx, h0, reset, theta, y, h_first, h_out, h_out_step, norm, norm_clip, stream
+    lib.pob_gru_sequence_forward.argtypes = [_VP, C.c_int, C.c_longlong, C.c_longlong, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                             _VP, C.c_int, _VP, C.c_float, _VP]
     if lib.pob_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {lib.pob_abi_version()} != {ABI_VERSION}; rebuild it")
     for name in EXPORTS:

@@ -351,17 +351,24 @@ def _normalizer_to_update(policy, update_normalizer: bool, n_rows: int) -> bool:
     return True
 
 
-def _critic_buffers(roll, critic, gae, record_truncation: bool, state, T: int, B: int, D: int, dev) -> torch.Tensor:
+def _critic_buffers(roll, critic, gae, record_truncation: bool, state, T: int, B: int, D: int, dev,
+                    recurrent: bool = False) -> torch.Tensor:
     """The ``critic=``, ``gae=``, ``record_truncation=`` arguments of the actor rollouts: checks
     them, allocates what they add to the trajectory and returns the (T, B, D) observation rows --
-    with a critic the first T of a (T + 1, B, D) buffer whose last is ``roll.final_obs``."""
+    with a critic the first T of a (T + 1, B, D) buffer whose last is ``roll.final_obs``.
+    ``recurrent``: the rollout takes a ``RecurrentValueFunction`` too; it then gains the critic's
+    (T + 1, B) reset rows (``roll._reset_rows``: row 0 the critic's, rows 1 .. T the trajectory's
+    ``done``) and ``roll.value_hidden0``."""
     f = dict(dtype=torch.float32, device=dev)
     roll.critic = critic
     if critic is None and gae is not None:
         raise ValueError("gae= needs critic=")
     if critic is not None:
-        from .training.gae import ValueFunction, gae_options
-        if not isinstance(critic, ValueFunction):
+        from .training.gae import RecurrentValueFunction, ValueFunction, gae_options
+        if recurrent:
+            if not isinstance(critic, (ValueFunction, RecurrentValueFunction)):
+                raise TypeError("critic must be a training.gae.ValueFunction or RecurrentValueFunction")
+        elif not isinstance(critic, ValueFunction):
             raise TypeError("critic must be a training.gae.ValueFunction")
         if critic.obs_size != D:
             raise ValueError(f"the critic is for observations of width {critic.obs_size}, the rollout records {D}")
@@ -381,6 +388,10 @@ def _critic_buffers(roll, critic, gae, record_truncation: bool, state, T: int, B
     roll.values = torch.empty((T + 1, B), **f)
     roll.vs = torch.empty((T, B), **f)
     roll.advantages = torch.empty((T, B), **f)
+    if recurrent and isinstance(critic, RecurrentValueFunction):
+        critic._buffers(B)  # hidden and reset exist before the capture
+        roll._reset_rows = torch.empty((T + 1, B), **f)
+        roll.value_hidden0 = torch.empty((B, critic.hidden_size), **f)
     return roll._obs_buffer[:T]
 
 
@@ -397,7 +408,15 @@ def _critic_pass(roll) -> None:
         return
     from . import _lib
     T, B = roll.steps, int(roll.values.shape[1])
-    roll.critic.values_into(roll._obs_buffer.view((T + 1) * B, -1), roll.values.view(-1))
+    if getattr(roll, "_reset_rows", None) is not None:
+        # The recurrent critic: the rows in time order in ONE launch, from the state the last replay's
+        # T trajectory rows left (final_obs is the next replay's obs[0]: it must not advance the carry).
+        critic = roll.critic
+        roll._reset_rows[0].copy_(critic.reset)
+        critic.values_sequence_into(roll._obs_buffer, roll._reset_rows, roll.values, roll.value_hidden0, carry_step=T)
+        critic.reset.copy_(roll.done[T - 1])
+    else:
+        roll.critic.values_into(roll._obs_buffer.view((T + 1) * B, -1), roll.values.view(-1))
     o = roll.gae
     _lib.check(_lib.lib.pob_gae(T, B, _lib.ptr(roll.truncation), _lib.ptr(roll.done), 1, _lib.ptr(roll.reward),
                                 o["reward_scaling"], _lib.ptr(roll.values), _lib.ptr(roll.values[T]), o["lambda_"],
@@ -424,8 +443,15 @@ class RecurrentActorRollout:
     kernel writes) instead of ``state.obs``; ``roll.obs`` then holds those columns.
     Single-kind ``create(...)`` chains only.  ``update_normalizer=True``: as ``ActorRollout``
     (with ``masked=True`` the policy's normaliser is one over the masked columns).  ``critic=``,
-    ``gae=``, ``record_truncation=``: as ``ActorRollout``; the critic is feed-forward, of the
-    recorded observation's width (the masked columns' with ``masked=True``)."""
+    ``gae=``, ``record_truncation=``: as ``ActorRollout``; the critic is of the recorded observation's
+    width (the masked columns' with ``masked=True``), a feed-forward ``ValueFunction`` or a
+    ``training.gae.RecurrentValueFunction`` (DESIGN.md "Recurrent critic").  The recurrent one sees the
+    (T + 1) B rows in time order, in ONE ``pob_gru_sequence_forward`` launch where the feed-forward
+    launch sits: ``roll.values[t]`` is its value of ``obs[t]`` given everything it saw since the episode
+    began, across replays (its reset rows are ``[critic.reset, done[0], .., done[T - 1]]``);
+    ``roll.value_hidden0`` (B, H) is the post-reset state row 0 started from (the learner's BPTT restarts
+    there); ``critic.hidden`` is left as the state after the T trajectory rows -- ``final_obs`` is the
+    next replay's ``obs[0]`` and does not advance it -- and ``critic.reset`` as ``done[T - 1]``."""
 
     def __init__(self, env, state, policy, steps: int, masked: bool = False, update_normalizer: bool = False,
                  critic=None, gae=None, record_truncation: bool = False):
@@ -450,13 +476,15 @@ class RecurrentActorRollout:
         dev, T = obs.device, self.steps
         policy._buffers(B)  # hidden and reset exist before the capture
         self.update_normalizer = _normalizer_to_update(policy, update_normalizer, T * B)
-        self.obs = _critic_buffers(self, critic, gae, record_truncation, state, T, B, D, dev)
+        self.obs = _critic_buffers(self, critic, gae, record_truncation, state, T, B, D, dev, recurrent=True)
         self.actions = torch.empty((T, B, A), dtype=torch.float32, device=dev)
         self.raw = torch.empty((T, B, A), dtype=torch.float32, device=dev)
         self.logp = torch.zeros((T, B), dtype=torch.float32, device=dev)
         self.hidden = torch.empty((T, B, H), dtype=torch.float32, device=dev)
         self.reward = torch.empty((T, B), dtype=torch.float32, device=dev)
-        self.done = torch.empty((T, B), dtype=torch.float32, device=dev)
+        # under a recurrent critic done is rows 1 .. T of its reset rows: no copy of the trajectory's done
+        rows = getattr(self, "_reset_rows", None)
+        self.done = torch.empty((T, B), dtype=torch.float32, device=dev) if rows is None else rows[1:]
         torch.cuda.synchronize(dev)
         self.graph = torch.cuda.CUDAGraph()
         with no_gc(), torch.cuda.graph(self.graph):

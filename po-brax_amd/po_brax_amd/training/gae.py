@@ -9,6 +9,10 @@ carries a graph (brax stops the gradient on both).
 ``ValueFunction`` wraps a ``make_model`` network of last width 1 for the actor rollouts' critic
 pass: ``values_into`` is one ``pob_mlp_forward_norm`` launch over (N, D) observation rows.
 Formula, operation order and what is pinned: DESIGN.md "Critic pass and GAE".
+
+``RecurrentValueFunction`` is the critic with a memory (DESIGN.md "Recurrent critic"): a
+``make_recurrent_model`` network of last width 1 and its carried GRU state; ``values_sequence_into``
+is one ``pob_gru_sequence_forward`` launch over (S, B, D) trajectory rows in time order.
 """
 from __future__ import annotations
 
@@ -19,7 +23,7 @@ import torch
 from .. import _lib
 from .._lib import check, lib, ptr
 from . import normalization as _normalization
-from .networks import FeedForwardModel, Params
+from .networks import FeedForwardModel, Params, RecurrentModel, RecurrentParams
 
 
 def _gae_torch(truncation, termination, rewards, values, bootstrap_value, lambda_, discount, reward_scaling, vs, adv):
@@ -149,3 +153,64 @@ class ValueFunction:
         rows = obs.detach().reshape(-1, self.obs_size).contiguous()
         out = torch.empty((rows.shape[0],), dtype=torch.float32, device=rows.device)
         return self.values_into(rows, out).reshape(obs.shape[:-1])
+
+
+class RecurrentValueFunction:
+    """The critic of a ``RecurrentActorRollout`` that remembers: a ``make_recurrent_model`` network whose
+    last post-MLP width is 1.  It owns ``hidden`` (B, H), the GRU state carried from call to call, and
+    ``reset`` (B,): where it is non-zero the env's next window starts from h = 0.  Both are allocated at
+    first use and start as zeros (``RecurrentTanhPolicy``'s rule); after that no allocation and no host
+    sync: capture-safe.  ``params.theta`` and the table of ``normalizer`` are read at launch time, as
+    ``ValueFunction``'s."""
+
+    def __init__(self, model: RecurrentModel, params: RecurrentParams, normalizer=None):
+        if getattr(model, "gru", None) is None or getattr(model, "post_sizes", None) is None:
+            raise ValueError("model must come from make_recurrent_model")
+        if model.post_sizes[-1] != 1:
+            raise ValueError(f"the value network's last width must be 1, got {model.post_sizes[-1]}")
+        theta = params.theta
+        self.obs_size, self.hidden_size = model.pre_sizes[0], model.hidden_size
+        self.normalizer = _normalization.attach(normalizer, self.obs_size, theta.device)
+        if not (theta.is_cuda and theta.dtype == torch.float32 and theta.is_contiguous()):
+            raise ValueError("params.theta must be a contiguous float32 CUDA tensor (params.to('cuda'))")
+        if theta.numel() != model.gru.param_count:
+            raise ValueError(f"theta has {theta.numel()} elements, the network {model.gru.param_count}")
+        self.model, self.params, self.theta = model, params, theta
+        self.hidden = self.reset = None
+
+    def _buffers(self, B: int):
+        if self.hidden is None or self.hidden.shape[0] != B:
+            dev = self.theta.device
+            self.hidden = torch.zeros((B, self.hidden_size), dtype=torch.float32, device=dev)
+            self.reset = torch.zeros((B,), dtype=torch.float32, device=dev)
+
+    def values_sequence_into(self, obs: torch.Tensor, reset: torch.Tensor, values: torch.Tensor,
+                             h_first: Optional[torch.Tensor] = None, carry_step: Optional[int] = None) -> torch.Tensor:
+        """``values`` (S, B) <- the value of every row of ``obs`` (S, B, D) in time order, env b starting
+        from ``self.hidden[b]`` and from h = 0 at every step s with ``reset[s][b] != 0`` (reset (S, B)):
+        ONE ``pob_gru_sequence_forward`` launch.  ``h_first`` (B, H) receives the state row 0 started from,
+        after ``reset[0]``; ``self.hidden`` is overwritten in place with the state after ``carry_step``
+        steps (1 .. S; None: S).  All contiguous float32 tensors on the parameters' device."""
+        dev, D, H = self.theta.device, self.obs_size, self.hidden_size
+
+        def ok(t, shape):
+            return (isinstance(t, torch.Tensor) and tuple(t.shape) == shape and t.dtype == torch.float32
+                    and t.is_contiguous() and t.device == dev)
+
+        if not (isinstance(obs, torch.Tensor) and obs.dim() == 3 and obs.shape[0] >= 1 and obs.shape[1] >= 1
+                and ok(obs, (obs.shape[0], obs.shape[1], D))):
+            raise ValueError(f"obs must be a contiguous float32 tensor (S, B, {D}) on {dev}")
+        S, B = int(obs.shape[0]), int(obs.shape[1])
+        for name, t, shape in (("reset", reset, (S, B)), ("values", values, (S, B)), ("h_first", h_first, (B, H))):
+            if not (ok(t, shape) or (name == "h_first" and t is None)):
+                raise ValueError(f"{name} must be a contiguous float32 tensor {shape} on {dev}")
+        step = S if carry_step is None else int(carry_step)
+        if not 1 <= step <= S:
+            raise ValueError(f"carry_step must be in 1 .. {S}, got {carry_step}")
+        self._buffers(B)
+        norm = self.normalizer
+        check(lib.pob_gru_sequence_forward(self.model.gru.handle, S, B, B, ptr(obs), None, ptr(self.hidden), ptr(reset),
+                                           ptr(self.theta), ptr(values), ptr(h_first), ptr(self.hidden), step,
+                                           None if norm is None else ptr(norm.table), 0.0 if norm is None else norm.clip,
+                                           _lib.stream_handle(dev)))
+        return values

@@ -36,7 +36,7 @@ import torch
 from .. import _lib
 from .._lib import check, lib, ptr
 from . import networks as _networks
-from .gae import ValueFunction
+from .gae import RecurrentValueFunction, ValueFunction
 
 MAX_ACTION_SIZE = 128  # POB_PPO_MAX_A
 CHUNK = 1024           # POB_PPO_CHUNK
@@ -448,7 +448,7 @@ class RecurrentPPOLearner:
             roll.replay()
             metrics = learner.update(roll)
 
-    ``policy`` is a ``RecurrentTanhPolicy``, ``value_fn`` the feed-forward ``ValueFunction``.  Minibatches
+    ``policy`` is a ``RecurrentTanhPolicy``, ``value_fn`` a ``ValueFunction`` (or a recurrent one: below).  Minibatches
     are drawn over ENVS, not rows: per epoch one device permutation of the B envs, cut into
     ``num_minibatches`` slices of M = B / num_minibatches envs; a minibatch is the whole T-step window
     of its envs, run through the recurrent network from ``roll.hidden[0]`` (the post-reset state step 0
@@ -462,27 +462,40 @@ class RecurrentPPOLearner:
     ``model.apply_sequence`` under autograd on the gathered, normalised rows (CPU tensors too) and
     ``"native"`` is ``model.apply_sequence_native`` (``pob_gru_sequence_forward_train`` /
     ``pob_gru_sequence_backward``, the trajectory read in place: DESIGN.md "Recurrent backward"); for
-    the value network they are ``PPOLearner``'s.  The default is ``("native", "torch")``.  Measured on an
+    a feed-forward value network they are ``PPOLearner``'s.  The default (``"auto"``) is then ``("native",
+    "torch")``.  Measured on an
     MI355X (DESIGN.md "Recurrent backward"): a window of T = 20 steps of 2 048 envs, forward with grad plus
     backward, takes 3.09 ms natively against 12.3 ms in torch ops (114 -> GRU 64 -> 16; 2.35 against 12.4 ms
     at 30 columns), and one update of 32 such minibatches 172 ms against 403 ms for ``"torch"`` and 254 ms
     for ``"native"``; the value half stays ``"torch"`` (DESIGN.md "MLP backward": the vendor GEMMs win at
     width 256).
 
+    ``value_fn`` may be a ``RecurrentValueFunction`` (DESIGN.md "Recurrent critic"): the value network is
+    then unrolled over the same windows as the policy, from ``roll.value_hidden0`` (the post-reset state
+    the critic's row 0 started from) with the same ``reset`` and ``idx``; its ``"torch"`` is
+    ``apply_sequence`` on the gathered, normalised rows, its ``"native"`` ``apply_sequence_native``, (T, M, 1)
+    read as the loss's T M rows.  The default is then ``("native", "native")``: the GRU window is 4 - 5.3 x
+    faster natively, and the vendor-GEMM argument holds for 256-wide dense layers only.  There is no
+    gradient to ``value_hidden0``.
+
     Not brax's: advantages and value targets are the replay's, minibatches never cut a window shorter
     than T, and the permutation is torch's."""
 
     def __init__(self, policy, value_fn, learning_rate: float = 3e-4, entropy_cost: float = 1e-4,
                  ppo_epsilon: float = 0.3, num_minibatches: int = 32, num_update_epochs: int = 4, key=None,
-                 backward=("native", "torch")):
-        pair = (backward, backward) if isinstance(backward, str) else backward
-        if not (isinstance(pair, (tuple, list)) and len(pair) == 2 and all(b in ("torch", "native") for b in pair)):
-            raise ValueError(f"backward must be 'torch', 'native' or a (policy, value) pair of those, got {backward!r}")
-        self.backward = tuple(pair)
+                 backward="auto"):
         if not isinstance(policy, _networks.RecurrentTanhPolicy):
             raise TypeError("policy must be a training.networks.RecurrentTanhPolicy (the recurrent actor)")
-        if not isinstance(value_fn, ValueFunction):
-            raise TypeError("value_fn must be a training.ValueFunction")
+        if not isinstance(value_fn, (ValueFunction, RecurrentValueFunction)):
+            raise TypeError("value_fn must be a training.ValueFunction or a training.RecurrentValueFunction")
+        self.recurrent_critic = isinstance(value_fn, RecurrentValueFunction)
+        if isinstance(backward, str) and backward == "auto":
+            backward = ("native", "native") if self.recurrent_critic else ("native", "torch")
+        pair = (backward, backward) if isinstance(backward, str) else backward
+        if not (isinstance(pair, (tuple, list)) and len(pair) == 2 and all(b in ("torch", "native") for b in pair)):
+            raise ValueError("backward must be 'auto', 'torch', 'native' or a (policy, value) pair of the last two, "
+                             f"got {backward!r}")
+        self.backward = tuple(pair)
         if key is None:
             raise ValueError("key is required (jumpy.random_prngkey)")
         if int(num_minibatches) < 1 or int(num_update_epochs) < 1:
@@ -507,6 +520,9 @@ class RecurrentPPOLearner:
         for name in ("obs", "raw", "logp", "advantages", "vs", "hidden", "done"):
             if not isinstance(getattr(roll, name, None), torch.Tensor):
                 raise ValueError(f"roll has no {name}: build a RecurrentActorRollout with critic=")
+        if self.recurrent_critic and not isinstance(getattr(roll, "value_hidden0", None), torch.Tensor):
+            raise ValueError("roll has no value_hidden0: build the RecurrentActorRollout with "
+                             "critic=RecurrentValueFunction(...)")
         T, B = int(roll.logp.shape[0]), int(roll.logp.shape[1])
         N, A, D = T * B, self.policy.action_size, self.policy.obs_size
         if B % self.num_minibatches:
@@ -523,16 +539,20 @@ class RecurrentPPOLearner:
         model, v_model = self.policy.model, self.value_fn.model
         p_params = types.SimpleNamespace(theta=self._theta[0])
         v_params = types.SimpleNamespace(theta=self._theta[1])
-        v_apply = v_model.apply_native if self.backward[1] == "native" else v_model.apply
+        v_h0 = roll.value_hidden0 if self.recurrent_critic else None
+        # the native windows read the trajectory in place: no gathered rows when both halves are such
+        gathered = not (self.recurrent_critic and self.backward == ("native", "native"))
+        v_apply = None if self.recurrent_critic else (v_model.apply_native if self.backward[1] == "native" else v_model.apply)
         metrics = None
         for _ in range(self.num_update_epochs):
             perm = torch.randperm(B, device=dev, generator=self._generator).to(torch.int32)
             for m in range(self.num_minibatches):
                 idx = perm[m * M:(m + 1) * M].contiguous()
                 rows = (row0 + idx.reshape(1, M)).reshape(T * M)  # (t, m) order: trajectory row t B + idx[m]
-                x = obs.index_select(0, rows)
-                x_p = x if norm is None else norm.apply(x)
-                x_v = x_p if v_norm is norm else (x if v_norm is None else v_norm.apply(x))
+                if gathered:
+                    x = obs.index_select(0, rows)
+                    x_p = x if norm is None else norm.apply(x)
+                    x_v = x_p if v_norm is norm else (x if v_norm is None else v_norm.apply(x))
                 with torch.enable_grad():
                     if self.backward[0] == "native":
                         y, _ = model.apply_sequence_native(p_params, obs3, h0, reset, idx, norm)
@@ -541,7 +561,14 @@ class RecurrentPPOLearner:
                         y, _ = model.apply_sequence(p_params, x_p.reshape(T, M, D), h0.index_select(0, j),
                                                     reset.index_select(1, j))
                     logits = y.reshape(T * M, 2 * A)
-                    values = v_apply(v_params, x_v).reshape(T * M)
+                    if not self.recurrent_critic:
+                        values = v_apply(v_params, x_v).reshape(T * M)
+                    elif self.backward[1] == "native":
+                        values = v_model.apply_sequence_native(v_params, obs3, v_h0, reset, idx, v_norm)[0].reshape(T * M)
+                    else:
+                        j = idx.long()
+                        values = v_model.apply_sequence(v_params, x_v.reshape(T, M, D), v_h0.index_select(0, j),
+                                                        reset.index_select(1, j))[0].reshape(T * M)
                     total, metrics = ppo_loss(logits, values, raw, logp, adv, vs, self.key, idx=rows,
                                               entropy_cost=self.entropy_cost, ppo_epsilon=self.ppo_epsilon)
                 self.optimizer.zero_grad(set_to_none=True)
