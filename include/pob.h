@@ -193,6 +193,8 @@ int pob_random_split_batch(const uint32_t *keys, int B, int num, uint32_t *out, 
 /* uniform(key, (n,), lo, hi) elements [first, first+count) */
 int pob_random_uniform(const uint32_t *key, int n, int first, int count, float lo, float hi, float *out,
                        void *stream);
+/* random_bits(key, (n,)) elements [first, first+count): the uint32 words uniform draws are made from */
+int pob_random_bits(const uint32_t *key, int n, int first, int count, uint32_t *out, void *stream);
 /* bench/rollout helper: key_io <- split(key_io)[0]; act = uniform(split(key_io)[1], (total,A), -1, 1)
  * rows [first, first+B) (a shard of a batch of `total` envs) */
 int pob_random_actions(uint32_t *key_io, int total, int first, int B, int A, float *act, void *stream);
@@ -395,6 +397,28 @@ int pob_gru_sequence_forward(const pob_gru *g, int S, long long M, long long B, 
                              float *y /* (S, M, out) */, float *h_first /* (M, H), may be NULL */,
                              float *h_out /* (M, H), may be NULL */, int h_out_step,
                              const float *norm /* may be NULL */, float norm_clip, void *stream);
+
+/* ---- Fused Adam (ABI v8, additive): one optimiser step of up to POB_ADAM_MAX_SEG parameter
+ * vectors in one launch, adam_step_ref of csrc/pob_mlp.h bit for bit (DESIGN.md "Learner on the
+ * device": optax's adam [ext], the float32 operation order).  segs is a HOST array of n_seg
+ * segments; it is copied into the kernel's argument, so nothing of it is read after the call
+ * returns.  Per segment theta, m and v (n floats each, device memory, 4-byte aligned, any n >= 1)
+ * are updated IN PLACE from grad; segments must not overlap.  state is two float64 words of device
+ * memory, {beta1^t, beta2^t} as running products, 1.0 each before the first step: the call reads
+ * them, applies the bias corrections of step t + 1, and a one-lane launch behind it stores the
+ * advanced products, so the step count lives on the device and a replayed graph counts on.
+ * Arguments are checked before any HIP call; no allocation, no atomics, no synchronisation:
+ * capturable. */
+#define POB_ADAM_MAX_SEG 4
+typedef struct pob_adam_seg {
+  float *theta;
+  const float *grad;
+  float *m;
+  float *v;
+  long long n;
+} pob_adam_seg;
+int pob_adam_step(const pob_adam_seg *segs, int n_seg, double *state, float lr, float beta1, float beta2, float eps,
+                  void *stream);
 
 #ifdef __cplusplus
 }

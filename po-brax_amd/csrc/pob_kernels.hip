@@ -2787,6 +2787,11 @@ __global__ void k_uniform(const uint32_t *key, int n, int first, int count, floa
   if (i >= count) return;
   out[i] = tf_uniform(key[0], key[1], (uint32_t)n, (uint32_t)(first + i), lo, hi);
 }
+__global__ void k_bits(const uint32_t *key, int n, int first, int count, uint32_t *out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  out[i] = tf_elem(key[0], key[1], (uint32_t)n, (uint32_t)(first + i));
+}
 // act = uniform(split(key)[1], (total, A), -1, 1)[first:first+B]
 __global__ void k_actions(const uint32_t *key, int total, int first, int B, int A, float *act) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3301,6 +3306,14 @@ int pob_random_uniform(const uint32_t *key, int n, int first, int count, float l
   if (count == 0) return POB_OK;
   hipLaunchKernelGGL(k_uniform, grid_for(count, 256), dim3(256), 0, (hipStream_t)stream, key, n, first, count, lo, hi, out);
   return hip_check(hipGetLastError(), "k_uniform launch");
+}
+
+int pob_random_bits(const uint32_t *key, int n, int first, int count, uint32_t *out, void *stream) {
+  if (!key || !out) return fail(POB_EINVAL, "NULL argument");
+  if (n <= 0 || first < 0 || count < 0 || first > n - count) return fail(POB_EINVAL, "bad bits range");
+  if (count == 0) return POB_OK;
+  hipLaunchKernelGGL(k_bits, grid_for(count, 256), dim3(256), 0, (hipStream_t)stream, key, n, first, count, out);
+  return hip_check(hipGetLastError(), "k_bits launch");
 }
 
 int pob_random_actions(uint32_t *key_io, int total, int first, int B, int A, float *act, void *stream) {

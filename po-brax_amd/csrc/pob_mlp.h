@@ -2,10 +2,10 @@
 // (pob_mlp.hip: k_mlp_forward, k_policy_act, the recurrent k_gru_forward, k_gru_policy_act, the
 // observation normaliser's k_obsnorm_*, k_gae, k_ppo_* and the training forward / backward pass
 // k_mlp_forward_train, k_mlp_bwd_*, and the recurrent window's k_gru_seq_forward, k_gru_seq_backward,
-// k_gru_bwd_weights, k_gru_seq_infer).
+// k_gru_bwd_weights, k_gru_seq_infer, and the optimiser's k_adam_step).
 // Compiled for the device by hipcc and, with POB_MLP_HOST, for the host by g++
 // (tests/host/mlp_host.cpp, gru_host.cpp, obsnorm_host.cpp, gae_host.cpp, ppo_host.cpp,
-// mlp_bwd_host.cpp, gru_bwd_host.cpp, gru_seq_infer_host.cpp); both with -ffp-contract=off.
+// mlp_bwd_host.cpp, gru_bwd_host.cpp, gru_seq_infer_host.cpp, adam_host.cpp); both with -ffp-contract=off.
 //
 // Every function is a fixed sequence of float32 +, *, fmaf, integer bit operations, and the
 // correctly rounded reciprocal and square root (pob_rcp / pob_sqrt of pob_math.h on the device,
@@ -319,7 +319,48 @@ POB_MLP_D void pob_ppo_finish(const double S_p, const double S_v, const double S
   losses[3] = entropy;
 }
 
+// ---------------------------------------------------------------------------- Adam
+// optax's adam [ext] (brax v1 PPO's optimiser; no weight decay, no amsgrad) in a fixed float32
+// order (DESIGN.md "Learner on the device").  The step count lives in the state block as the two
+// running float64 products P1 = beta1^t, P2 = beta2^t (from 1.0; P <- P (double)beta, one float64
+// product a step), so there is no counter and no pow.  Per step, once: the new products, c = (float)
+// (1.0 - P) rounded once from float64, and the bias corrections as reciprocals ic = 1 / c.  Per
+// element: m = fmaf(beta1, m, (1 - beta1) g), v = fmaf(beta2, v, ((1 - beta2) g) g), m_hat = m ic1,
+// v_hat = v ic2, theta = fmaf(-lr, m_hat (1 / (sqrt(v_hat) + eps)), theta): every quotient is a
+// product with a correctly rounded reciprocal, and 1 - beta is one float32 subtraction.
+#define POB_ADAM_MAX_SEG 4  // (theta, grad, m, v, n) segments of one launch
+POB_MLP_D void pob_adam_bias(const double p1, const double p2, const float beta1, const float beta2, double &p1_new,
+                             double &p2_new, float &ic1, float &ic2) {
+  p1_new = p1 * (double)beta1;
+  p2_new = p2 * (double)beta2;
+  ic1 = mlp_rcp((float)(1.0 - p1_new));
+  ic2 = mlp_rcp((float)(1.0 - p2_new));
+}
+POB_MLP_D void pob_adam_elem(float &theta, const float g, float &m, float &v, const float lr, const float beta1,
+                             const float beta2, const float eps, const float ic1, const float ic2) {
+  m = MLP_FMA(beta1, m, (1.0f - beta1) * g);
+  v = MLP_FMA(beta2, v, ((1.0f - beta2) * g) * g);
+  const float m_hat = m * ic1, v_hat = v * ic2;
+  const float den = mlp_sqrt(v_hat) + eps;
+  theta = MLP_FMA(-lr, m_hat * mlp_rcp(den), theta);
+}
+
 #ifdef POB_MLP_HOST
+// One Adam step of n_seg <= POB_ADAM_MAX_SEG segments: theta, m, v (n[s] floats each) updated in
+// place from grad, all under the bias corrections of ONE advance of state[2] = {beta1^t, beta2^t},
+// which is stored back.  Segments share nothing else.
+static inline void adam_step_ref(const int n_seg, float *const *theta, const float *const *grad, float *const *m,
+                                 float *const *v, const long long *n, double *state, const float lr, const float beta1,
+                                 const float beta2, const float eps) {
+  double p1, p2;
+  float ic1, ic2;
+  pob_adam_bias(state[0], state[1], beta1, beta2, p1, p2, ic1, ic2);
+  for (int s = 0; s < n_seg; ++s)
+    for (long long i = 0; i < n[s]; ++i) pob_adam_elem(theta[s][i], grad[s][i], m[s][i], v[s][i], lr, beta1, beta2, eps, ic1, ic2);
+  state[0] = p1;
+  state[1] = p2;
+}
+
 // The PPO loss of M minibatch rows: logits (M, 2 A), values (M), u (M, A) the entropy draws
 // (uniform(split(key)[1], (M, A), -1, 1) on the device); raw (N, A), old_logp, advantages, vs (N)
 // in trajectory order, row i reading trajectory row idx[i] (NULL: i).  dlogits (M, 2 A), dvalues

@@ -830,6 +830,114 @@ int pob_gae(int T, long long B, const float *truncation, const float *second, in
 
 }  // extern "C"
 
+// ============================================================================ Adam
+// adam_step_ref of pob_mlp.h (the specification; DESIGN.md "Learner on the device").  One launch
+// steps every segment: the table travels BY VALUE as the kernel argument (a captured graph keeps the
+// copy; no device pointer array that could go stale).  The work is streaming, 28 bytes an element: a
+// lane owns ONE item, either a 16-byte group of four elements of the segment's aligned body (four
+// 16-byte loads in flight, three 16-byte stores; consecutive lanes on consecutive groups) or one
+// scalar element of its head or tail.  A segment's base is only 4-byte aligned: the host finds the
+// head that brings theta, grad, m and v to a 16-byte boundary TOGETHER, and a segment whose four
+// bases disagree modulo 16 is all head (scalar).  A block serves one segment (blk0: its first block),
+// found by a select over the table, not by indexing it (no scratch).  Every lane forms the step's bias
+// corrections from the state block itself (two uniform 8-byte loads, two float64 products); the
+// block is advanced by k_adam_advance, one lane, after it on the same stream, so a replayed graph
+// counts its own steps.  No LDS, no atomics, ordinary vector stores only.
+#define ADAM_THREADS 256
+struct AdamSeg {
+  float *theta, *m, *v;
+  const float *grad;
+  long long head, nvec, nsc;  // scalar elements before the body, 16-byte groups, scalar elements in all
+  unsigned blk0;
+};
+struct AdamTable {
+  AdamSeg seg[POB_ADAM_MAX_SEG];
+  int n_seg;
+};
+
+__global__ __launch_bounds__(ADAM_THREADS) void k_adam_step(const AdamTable t, const double *state, const float lr,
+                                                            const float beta1, const float beta2, const float eps) {
+  AdamSeg s = t.seg[0];
+#pragma unroll
+  for (int k = 1; k < POB_ADAM_MAX_SEG; ++k)
+    if (k < t.n_seg && blockIdx.x >= t.seg[k].blk0) s = t.seg[k];
+  const long long item = (long long)(blockIdx.x - s.blk0) * ADAM_THREADS + threadIdx.x;
+  if (item >= s.nvec + s.nsc) return;
+  double p1, p2;
+  float ic1, ic2;
+  pob_adam_bias(state[0], state[1], beta1, beta2, p1, p2, ic1, ic2);
+  if (item < s.nvec) {
+    const size_t e = (size_t)s.head + 4 * (size_t)item;
+    float4 th = *(const float4 *)(s.theta + e), m = *(const float4 *)(s.m + e), v = *(const float4 *)(s.v + e);
+    const float4 g = *(const float4 *)(s.grad + e);
+    pob_adam_elem(th.x, g.x, m.x, v.x, lr, beta1, beta2, eps, ic1, ic2);
+    pob_adam_elem(th.y, g.y, m.y, v.y, lr, beta1, beta2, eps, ic1, ic2);
+    pob_adam_elem(th.z, g.z, m.z, v.z, lr, beta1, beta2, eps, ic1, ic2);
+    pob_adam_elem(th.w, g.w, m.w, v.w, lr, beta1, beta2, eps, ic1, ic2);
+    *(float4 *)(s.theta + e) = th;
+    *(float4 *)(s.m + e) = m;
+    *(float4 *)(s.v + e) = v;
+  } else {
+    const long long k = item - s.nvec;  // scalar element k: the head's, then the tail's behind the body
+    const size_t e = (size_t)(k < s.head ? k : k + 4 * s.nvec);
+    float th = s.theta[e], m = s.m[e], v = s.v[e];
+    pob_adam_elem(th, s.grad[e], m, v, lr, beta1, beta2, eps, ic1, ic2);
+    s.theta[e] = th;
+    s.m[e] = m;
+    s.v[e] = v;
+  }
+}
+
+__global__ void k_adam_advance(double *state, const float beta1, const float beta2) {
+  double p1, p2;
+  float ic1, ic2;
+  pob_adam_bias(state[0], state[1], beta1, beta2, p1, p2, ic1, ic2);
+  state[0] = p1;
+  state[1] = p2;
+}
+
+extern "C" {
+
+int pob_adam_step(const pob_adam_seg *segs, int n_seg, double *state, float lr, float beta1, float beta2, float eps,
+                  void *stream) {
+  if (n_seg < 1 || n_seg > POB_ADAM_MAX_SEG) return pob_fail_msg(POB_EINVAL, "adam: 1 .. 4 segments a launch");
+  if (!segs || !state) return pob_fail_msg(POB_EINVAL, "adam: NULL argument (segs, state)");
+  if (((uintptr_t)state & 7) != 0) return pob_fail_msg(POB_EINVAL, "adam: the state block must be 8-byte aligned");
+  AdamTable t;
+  long long blocks = 0;
+  for (int k = 0; k < POB_ADAM_MAX_SEG; ++k) {
+    AdamSeg &s = t.seg[k];
+    if (k >= n_seg) {
+      s = AdamSeg{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0u};
+      continue;
+    }
+    const pob_adam_seg &in = segs[k];
+    if (!in.theta || !in.grad || !in.m || !in.v) return pob_fail_msg(POB_EINVAL, "adam: NULL segment pointer");
+    if (in.n < 1 || in.n > (1LL << 36)) return pob_fail_msg(POB_EINVAL, "adam: a segment holds 1 .. 2^36 elements");
+    const uintptr_t a[4] = {(uintptr_t)in.theta, (uintptr_t)in.grad, (uintptr_t)in.m, (uintptr_t)in.v};
+    for (int q = 0; q < 4; ++q)
+      if (a[q] & 3) return pob_fail_msg(POB_EINVAL, "adam: segment pointers must be 4-byte aligned");
+    const bool together = (a[0] & 15) == (a[1] & 15) && (a[0] & 15) == (a[2] & 15) && (a[0] & 15) == (a[3] & 15);
+    long long head = together ? (long long)(((16 - (a[0] & 15)) & 15) >> 2) : in.n;
+    if (head > in.n) head = in.n;
+    s.theta = in.theta; s.grad = in.grad; s.m = in.m; s.v = in.v;
+    s.head = head;
+    s.nvec = (in.n - head) / 4;
+    s.nsc = in.n - 4 * s.nvec;
+    s.blk0 = (unsigned)blocks;
+    blocks += (s.nvec + s.nsc + ADAM_THREADS - 1) / ADAM_THREADS;
+    if (blocks > INT_MAX) return pob_fail_msg(POB_EINVAL, "adam: too many elements for one launch");
+  }
+  t.n_seg = n_seg;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_adam_step, dim3((unsigned)blocks), dim3(ADAM_THREADS), 0, st, t, (const double *)state, lr, beta1,
+                     beta2, eps);
+  hipLaunchKernelGGL(k_adam_advance, dim3(1), dim3(1), 0, st, state, beta1, beta2);
+  return mlp_hip_check(hipGetLastError(), "k_adam_step launch");
+}
+
+}  // extern "C"
+
 // ============================================================================ PPO loss
 // ppo_loss_ref of pob_mlp.h (the specification; DESIGN.md "PPO loss").  k_ppo_loss: a block of
 // 256 lanes owns a tile of R consecutive minibatch rows, R = min(256, 1024 / A), so a lane has at

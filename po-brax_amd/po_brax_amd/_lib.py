@@ -52,12 +52,20 @@ class pob_state(C.Structure):
         "ovf_mark")]
 
 
+ADAM_MAX_SEG = 4  # POB_ADAM_MAX_SEG
+
+
+class pob_adam_seg(C.Structure):
+    _fields_ = [("theta", _VP), ("grad", _VP), ("m", _VP), ("v", _VP), ("n", C.c_longlong)]
+
+
 # Every symbol include/pob.h declares (checked by tests/test_lib_symbols.py).
 EXPORTS = (
     "pob_abi_version", "pob_last_error", "pob_default_params", "pob_env_create",
     "pob_env_destroy", "pob_release_deferred", "pob_env_dims", "pob_env_default_angle", "pob_reset", "pob_step",
     "pob_step_mixed", "pob_reset_where_done", "pob_reset_where_done_shard", "pob_default_qp",
-    "pob_random_split", "pob_random_split_batch", "pob_random_uniform", "pob_random_actions", "pob_obs_gather",
+    "pob_random_split", "pob_random_split_batch", "pob_random_uniform", "pob_random_bits", "pob_random_actions",
+    "pob_obs_gather",
     "pob_env_set_obs_mask",
     "pob_mlp_create", "pob_mlp_destroy", "pob_mlp_param_count", "pob_mlp_forward", "pob_policy_act",
     "pob_gru_create", "pob_gru_destroy", "pob_gru_param_count", "pob_gru_forward", "pob_gru_policy_act",
@@ -68,6 +76,7 @@ EXPORTS = (
     "pob_mlp_saved_bytes", "pob_mlp_forward_train", "pob_mlp_backward_workspace_bytes", "pob_mlp_backward",
     "pob_gru_sequence_saved_bytes", "pob_gru_sequence_forward_train", "pob_gru_sequence_backward_workspace_bytes",
     "pob_gru_sequence_backward", "pob_gru_sequence_forward",
+    "pob_adam_step",
 )
 
 
@@ -102,6 +111,7 @@ def _load():
     lib.pob_random_split.argtypes = [_VP, C.c_int, C.c_int, C.c_int, _VP, _VP]
     lib.pob_random_split_batch.argtypes = [_VP, C.c_int, C.c_int, _VP, _VP]
     lib.pob_random_uniform.argtypes = [_VP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _VP, _VP]
+    lib.pob_random_bits.argtypes = [_VP, C.c_int, C.c_int, C.c_int, _VP, _VP]
     lib.pob_random_actions.argtypes = [_VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP]
     lib.pob_obs_gather.argtypes = [_VP, C.c_int, C.c_int, _VP, C.c_int, _VP, _VP]
     lib.pob_env_set_obs_mask.argtypes = [_VP, C.POINTER(C.c_int32), C.c_int]
@@ -152,6 +162,8 @@ def _load():
     # gru, S, M, B, obs, idx, h0, reset, theta, y, h_first, h_out, h_out_step, norm, norm_clip, stream
     lib.pob_gru_sequence_forward.argtypes = [_VP, C.c_int, C.c_longlong, C.c_longlong, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                              _VP, C.c_int, _VP, C.c_float, _VP]
+    # segs (host array), n_seg, state, lr, beta1, beta2, eps, stream
+    lib.pob_adam_step.argtypes = [C.POINTER(pob_adam_seg), C.c_int, _VP, C.c_float, C.c_float, C.c_float, C.c_float, _VP]
     if lib.pob_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {lib.pob_abi_version()} != {ABI_VERSION}; rebuild it")
     for name in EXPORTS:

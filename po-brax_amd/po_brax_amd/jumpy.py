@@ -7,6 +7,8 @@ threefry scheme.  Keys are ``torch.uint32`` tensors of shape ``(..., 2)``.
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 from . import _lib
@@ -80,6 +82,58 @@ def random_uniform(key: torch.Tensor, shape=(), low: float = 0.0, high: float = 
         check(lib.pob_random_uniform(key.data_ptr(), n, 0, n, float(low), float(high), out.data_ptr(),
                                      _lib.stream_handle(key.device)))
     return out
+
+
+def random_bits(key: torch.Tensor, shape=()) -> torch.Tensor:
+    """jax.random.bits(key, shape) in uint32: the words ``random_uniform`` makes its floats from."""
+    key = _dev_key(key)
+    shape = tuple(shape) if not isinstance(shape, int) else (shape,)
+    n = 1
+    for s in shape:
+        n *= int(s)
+    out = torch.empty(shape, dtype=torch.uint32, device=key.device)
+    if n:
+        check(lib.pob_random_bits(key.data_ptr(), n, 0, n, out.data_ptr(), _lib.stream_handle(key.device)))
+    return out
+
+
+def permutation_rounds(n: int) -> int:
+    """Sort rounds of jax's ``_shuffle`` for n items: ceil(3 ln(max(1, n)) / ln(2^32 - 1)), i.e. 0 for
+    n = 1, 1 up to n = 1 625, 2 up to n = 2 642 245."""
+    return int(math.ceil(3.0 * math.log(max(1, int(n))) / math.log(2 ** 32 - 1)))
+
+
+def random_permutation(key: torch.Tensor, n: int) -> torch.Tensor:
+    """jax.random.permutation(key, n) -> int32 (n,), on the key's device ([ext], recalled: jax's
+    ``_shuffle``, the scheme of the reset kernels' ``choice`` continued over every round).  x starts
+    as arange(n); each of ``permutation_rounds(n)`` rounds takes ``key, sub = split(key)`` and sorts x
+    STABLY by ``random_bits(sub, (n,))``.  A device key takes the device threefry and
+    ``torch.sort(stable=True)`` on the words mapped to the signed order (no host work, no
+    synchronisation: capturable); a CPU key the host threefry and a stable argsort.  ``key`` itself
+    is only read."""
+    key = torch.as_tensor(key)
+    if key.dtype != torch.uint32 or key.numel() != 2:
+        raise TypeError("key must be a torch.uint32 tensor of 2 words (random_prngkey)")
+    n = int(n)
+    if not 1 <= n < 2 ** 31:
+        raise ValueError(f"n must be in 1 .. 2^31 - 1, got {n}")
+    key = key.reshape(2)
+    rounds = permutation_rounds(n)
+    if key.device.type != "cuda":
+        from .training.networks import _host_bits, _host_split
+        x = torch.arange(n, dtype=torch.int32)
+        for _ in range(rounds):
+            key, sub = _host_split(key)
+            x = x[torch.sort(_host_bits(sub, n), stable=True)[1]]
+        return x
+    key = key.contiguous()
+    x = torch.arange(n, dtype=torch.int32, device=key.device)
+    for _ in range(rounds):
+        key, sub = random_split(key)
+        # uint32 order -> int32 order: flip the top bit
+        signed = random_bits(sub, n).view(torch.int32) ^ (-2 ** 31)
+        x = x[torch.sort(signed, stable=True)[1]]
+    return x
 
 
 def random_actions_(key_io: torch.Tensor, total: int, first: int, act: torch.Tensor) -> torch.Tensor:

@@ -18,7 +18,8 @@ DESIGN.md "PPO loss".
 vectors in place, so the captured rollout graph acts under the new parameters at its next replay.
 Two deviations from brax: the advantages and value targets are the replay's and are not recomputed
 per minibatch (``compute_gae`` exists for a learner that wants that), and the permutation is
-torch's, not jax's.
+torch's, not jax's, unless ``permutation="threefry"`` asks for ``jumpy.random_permutation``;
+``optimizer="fused"`` steps both parameter vectors with one launch and no host step count.
 
 ``RecurrentPPOLearner`` is the same loop for a ``RecurrentTanhPolicy`` over a
 ``RecurrentActorRollout(..., critic=...)``: minibatches of envs, each the whole recorded window,
@@ -345,7 +346,47 @@ def ppo_loss(logits: torch.Tensor, values: torch.Tensor, raw: torch.Tensor, old_
     return total, {"policy_loss": policy, "value_loss": value, "entropy_loss": entropy}
 
 
-class PPOLearner:
+class _DeviceLearner:
+    """What both learners share of the device-resident update: the optimiser and permutation options
+    (DESIGN.md "Learner on the device")."""
+
+    def _init_options(self, key, learning_rate: float, optimizer: str, permutation: str) -> None:
+        if optimizer not in ("torch", "fused"):
+            raise ValueError(f"optimizer must be 'torch' or 'fused', got {optimizer!r}")
+        if permutation not in ("torch", "threefry"):
+            raise ValueError(f"permutation must be 'torch' or 'threefry', got {permutation!r}")
+        dev = self.policy.theta.device
+        self.key = _networks._key_words(key).to(dev).clone()
+        words = _networks._key_words(key).cpu()
+        self._generator = torch.Generator(device=dev)
+        self._generator.manual_seed((int(words[0]) << 32) | int(words[1]))
+        # leaves over the actors' own storage: the optimiser steps in place
+        self._theta = [self.policy.theta.detach().requires_grad_(True), self.value_fn.theta.detach().requires_grad_(True)]
+        if optimizer == "fused":
+            from .optim import FusedAdam
+            self.optimizer = FusedAdam(self._theta, lr=float(learning_rate))
+        else:
+            self.optimizer = torch.optim.Adam(self._theta, lr=float(learning_rate))
+        self.permutation = permutation
+        self.perm_key = None
+        if permutation == "threefry":  # random_split(key, 3)[2], on the key's device
+            if dev.type == "cuda":
+                from .. import jumpy
+                self.perm_key = jumpy.random_split_rows(self.key, 3, 2, 1).reshape(2)
+            else:
+                self.perm_key = _networks._host_split(words, 3)[2].to(torch.uint32)
+
+    def _draw_permutation(self, n: int, dev) -> torch.Tensor:
+        """One epoch's int32 permutation of n items on ``dev``."""
+        if self.permutation == "threefry":
+            from .. import jumpy
+            perm = jumpy.random_permutation(self.perm_key, n).to(dev)
+            _advance_key(self.perm_key)
+            return perm
+        return torch.randperm(n, device=dev, generator=self._generator).to(torch.int32)
+
+
+class PPOLearner(_DeviceLearner):
     """The minibatch loop of brax v1 PPO over one replay of an ``ActorRollout(..., critic=value_fn)``:
 
         learner = PPOLearner(policy, value_fn, key=jumpy.random_prngkey(7))
@@ -369,12 +410,20 @@ class PPOLearner:
     ops), the 256-wide value network ``"torch"`` (the native pass is 2.4 x slower than the vendor
     GEMMs), i.e. ``backward=("native", "torch")``: one update in 78 ms against 108 ms for the default.
 
+    ``optimizer``: ``"torch"`` (the default: ``torch.optim.Adam``) or ``"fused"`` (``training.optim.FusedAdam``:
+    both parameter vectors in one launch, the step count on the device).  ``permutation``: ``"torch"`` (the
+    default: ``randperm`` from a generator seeded with ``key``) or ``"threefry"``: ``perm_key =
+    random_split(key, 3)[2]`` lives on the device, each epoch draws ``jumpy.random_permutation(perm_key, T B)``
+    (jax's shuffle, [ext]) and then ``perm_key <- split(perm_key)[0]``; ``key`` and the entropy draws are the
+    same either way.  With both nothing of an update is decided on the host (DESIGN.md "Learner on the
+    device").
+
     Not brax's: advantages and value targets are the replay's (not recomputed per minibatch), and
-    the permutation is torch's (``randperm``), not jax's."""
+    by default the permutation is torch's (``randperm``), not jax's."""
 
     def __init__(self, policy, value_fn, learning_rate: float = 3e-4, entropy_cost: float = 1e-4,
                  ppo_epsilon: float = 0.3, num_minibatches: int = 32, num_update_epochs: int = 4, key=None,
-                 backward="torch"):
+                 backward="torch", optimizer: str = "torch", permutation: str = "torch"):
         pair = (backward, backward) if isinstance(backward, str) else backward
         if not (isinstance(pair, (tuple, list)) and len(pair) == 2 and all(b in ("torch", "native") for b in pair)):
             raise ValueError(f"backward must be 'torch', 'native' or a (policy, value) pair of those, got {backward!r}")
@@ -392,14 +441,7 @@ class PPOLearner:
         self.policy, self.value_fn = policy, value_fn
         self.entropy_cost, self.ppo_epsilon = float(entropy_cost), float(ppo_epsilon)
         self.num_minibatches, self.num_update_epochs = int(num_minibatches), int(num_update_epochs)
-        dev = policy.theta.device
-        self.key = _networks._key_words(key).to(dev).clone()
-        words = _networks._key_words(key).cpu()
-        self._generator = torch.Generator(device=dev)
-        self._generator.manual_seed((int(words[0]) << 32) | int(words[1]))
-        # leaves over the actors' own storage: the optimiser steps in place
-        self._theta = [policy.theta.detach().requires_grad_(True), value_fn.theta.detach().requires_grad_(True)]
-        self.optimizer = torch.optim.Adam(self._theta, lr=float(learning_rate))
+        self._init_options(key, learning_rate, optimizer, permutation)
 
     def update(self, roll) -> Dict[str, torch.Tensor]:
         """One learning phase over ``roll``'s buffers as the last replay left them; returns the last
@@ -421,7 +463,7 @@ class PPOLearner:
                             for m, b in zip((self.policy.model, self.value_fn.model), self.backward))
         metrics = None
         for _ in range(self.num_update_epochs):
-            perm = torch.randperm(N, device=obs.device, generator=self._generator).to(torch.int32)
+            perm = self._draw_permutation(N, obs.device)
             for m in range(self.num_minibatches):
                 idx = perm[m * M:(m + 1) * M]
                 x = obs.index_select(0, idx)
@@ -439,7 +481,7 @@ class PPOLearner:
         return metrics
 
 
-class RecurrentPPOLearner:
+class RecurrentPPOLearner(_DeviceLearner):
     """``PPOLearner`` for the recurrent actor: "replay, learn, replay" over a
     ``RecurrentActorRollout(..., critic=value_fn)``:
 
@@ -478,12 +520,14 @@ class RecurrentPPOLearner:
     faster natively, and the vendor-GEMM argument holds for 256-wide dense layers only.  There is no
     gradient to ``value_hidden0``.
 
+    ``optimizer`` and ``permutation`` are ``PPOLearner``'s; the threefry permutation is over the B envs.
+
     Not brax's: advantages and value targets are the replay's, minibatches never cut a window shorter
-    than T, and the permutation is torch's."""
+    than T, and by default the permutation is torch's."""
 
     def __init__(self, policy, value_fn, learning_rate: float = 3e-4, entropy_cost: float = 1e-4,
                  ppo_epsilon: float = 0.3, num_minibatches: int = 32, num_update_epochs: int = 4, key=None,
-                 backward="auto"):
+                 backward="auto", optimizer: str = "torch", permutation: str = "torch"):
         if not isinstance(policy, _networks.RecurrentTanhPolicy):
             raise TypeError("policy must be a training.networks.RecurrentTanhPolicy (the recurrent actor)")
         if not isinstance(value_fn, (ValueFunction, RecurrentValueFunction)):
@@ -505,14 +549,7 @@ class RecurrentPPOLearner:
         self.policy, self.value_fn = policy, value_fn
         self.entropy_cost, self.ppo_epsilon = float(entropy_cost), float(ppo_epsilon)
         self.num_minibatches, self.num_update_epochs = int(num_minibatches), int(num_update_epochs)
-        dev = policy.theta.device
-        self.key = _networks._key_words(key).to(dev).clone()
-        words = _networks._key_words(key).cpu()
-        self._generator = torch.Generator(device=dev)
-        self._generator.manual_seed((int(words[0]) << 32) | int(words[1]))
-        # leaves over the actors' own storage: the optimiser steps in place
-        self._theta = [policy.theta.detach().requires_grad_(True), value_fn.theta.detach().requires_grad_(True)]
-        self.optimizer = torch.optim.Adam(self._theta, lr=float(learning_rate))
+        self._init_options(key, learning_rate, optimizer, permutation)
 
     def update(self, roll) -> Dict[str, torch.Tensor]:
         """One learning phase over ``roll``'s buffers as the last replay left them; returns the last
@@ -545,7 +582,7 @@ class RecurrentPPOLearner:
         v_apply = None if self.recurrent_critic else (v_model.apply_native if self.backward[1] == "native" else v_model.apply)
         metrics = None
         for _ in range(self.num_update_epochs):
-            perm = torch.randperm(B, device=dev, generator=self._generator).to(torch.int32)
+            perm = self._draw_permutation(B, dev)
             for m in range(self.num_minibatches):
                 idx = perm[m * M:(m + 1) * M].contiguous()
                 rows = (row0 + idx.reshape(1, M)).reshape(T * M)  # (t, m) order: trajectory row t B + idx[m]
