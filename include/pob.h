@@ -298,6 +298,14 @@ int pob_gru_policy_act_norm(const pob_gru *g, int B, int total, int first, const
                             uint32_t *key_io, int deterministic, const float *reset, float *h_io, float *action,
                             float *logp, float *raw, float *logits, float *obs_copy, float *h_in_copy, const float *norm,
                             float norm_clip, void *stream);
+/* pob_mlp_forward / pob_mlp_forward_norm through the kernel laid out for wide layers over many
+ * rows (the value network over a whole trajectory; DESIGN.md "Wide forward"): four waves share 64
+ * rows and split each layer's output columns, so theta is read from L2 once per 64 rows.  The
+ * same arguments, the same error contract, every network pob_mlp_create accepts, and the same
+ * bits as those two for every B >= 1; theta and norm are read at launch time. */
+int pob_mlp_forward_wide(const pob_mlp *mlp, int B, const float *x, const float *theta, float *y, void *stream);
+int pob_mlp_forward_wide_norm(const pob_mlp *mlp, int B, const float *x, const float *theta, float *y,
+                              const float *norm, float norm_clip, void *stream);
 
 /* ---- generalised advantage estimation (ABI v8, additive): brax v1 PPO's compute_gae [ext] in one
  * launch, gae_ref of csrc/pob_mlp.h bit for bit (DESIGN.md "Critic pass and GAE": formula and

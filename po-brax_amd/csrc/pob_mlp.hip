@@ -2,7 +2,8 @@
 // tanh-normal actor of DESIGN.md "Policy networks".
 //
 //   k_mlp_forward   y = MLP(x): every layer in one launch
-//   k_policy_act    the same forward, then the tanh-normal head (brax NormalTanhDistribution [ext])
+//   k_mlp_forward_wide   the same, four waves on 64 rows: for wide layers over many rows (below)
+//   k_policy_act   the same forward, then the tanh-normal head (brax NormalTanhDistribution [ext])
 //   k_gru_forward, k_gru_policy_act   the recurrent actor (pre-MLP, GRU cell, post-MLP; below)
 //   k_mlp_forward_train, k_mlp_bwd_*  the training forward and the backward pass
 //   k_gru_seq_forward, k_gru_seq_backward, k_gru_bwd_weights   the recurrent window's (at the end)
@@ -101,33 +102,35 @@ POB_MLP_D void mlp_layer(const float *src, float *dst, const float *W, const flo
 }
 
 // rows [b0, b0 + valid) of a row-major (B, width) array <- features [f0, f0 + width) of an image
+// (ROWS rows at PITCH floats a feature, copied by a block of LANES lanes: the one-wave tile's by default)
+template <int ROWS = MLP_ROWS, int LANES = 64, int PITCH = MLP_PITCH>
 POB_MLP_D void mlp_tile_store(float *dst, const float *img, const int f0, const int width, const int b0, const int valid,
                               const int lane) {
   float *d = dst + (size_t)b0 * width;
-  for (int e = lane; e < MLP_ROWS * width; e += 64) {
+  for (int e = lane; e < ROWS * width; e += LANES) {
     const int row = e / width, col = e - row * width;
-    if (row < valid) d[e] = img[(f0 + col) * MLP_PITCH + row];
+    if (row < valid) d[e] = img[(f0 + col) * PITCH + row];
   }
 }
 
-// features [0, D) of an image <- rows [b0, b0 + 32) of a row-major (B, D) array x: coalesced
+// features [0, D) of an image <- rows [b0, b0 + ROWS) of a row-major (B, D) array x: coalesced
 // loads, MLP_STAGE in flight per lane, tail rows repeating the last valid one.  copy (may be
 // NULL) receives the valid rows as loaded.  reset (may be NULL): a row whose reset[b] != 0 is
 // staged as +0 in every feature.  NORM: the image takes pob_obsnorm_apply of the value, with the
 // column's mean and scale (rows 0 and 1 of the (3, D) table `norm`) loaded along with it; copy
-// keeps the raw row.
-template <bool NORM>
+// keeps the raw row.  ROWS, LANES, PITCH: as mlp_tile_store's.
+template <bool NORM, int ROWS = MLP_ROWS, int LANES = 64, int PITCH = MLP_PITCH>
 POB_MLP_D void mlp_tile_load(float *img, const float *x, const int D, const int b0, const int valid, float *copy,
                              const float *reset, const float *norm, const float clip, const int lane) {
-  // element e = row D + col of the tile's 32 contiguous rows; a lane's elements are 64 apart
-  const int dq = 64 / D, dr = 64 - dq * D;
+  // element e = row D + col of the tile's ROWS contiguous rows; a lane's elements are LANES apart
+  const int dq = LANES / D, dr = LANES - dq * D;
   int row = lane / D, col = lane - row * D;
-  for (int e0 = lane; e0 < MLP_ROWS * D; e0 += 64 * MLP_STAGE) {
+  for (int e0 = lane; e0 < ROWS * D; e0 += LANES * MLP_STAGE) {
     float v[MLP_STAGE], mu[NORM ? MLP_STAGE : 1], sc[NORM ? MLP_STAGE : 1];
     int at[MLP_STAGE];  // the element's place in the image (-1: past the tile), bit 30: a row to copy out
 #pragma unroll
     for (int u = 0; u < MLP_STAGE; ++u) {
-      const bool in_tile = e0 + 64 * u < MLP_ROWS * D;
+      const bool in_tile = e0 + LANES * u < ROWS * D;
       const int rr = row < valid ? row : valid - 1;  // tail rows repeat the last one
       v[u] = in_tile ? x[(size_t)(b0 + rr) * D + col] : 0.0f;
       if (reset) v[u] = (in_tile && reset[b0 + rr] != 0.0f) ? 0.0f : v[u];
@@ -135,14 +138,14 @@ POB_MLP_D void mlp_tile_load(float *img, const float *x, const int D, const int 
         mu[u] = in_tile ? norm[col] : 0.0f;
         sc[u] = in_tile ? norm[D + col] : 0.0f;
       }
-      at[u] = in_tile ? (col * MLP_PITCH + row) | (row < valid ? 1 << 30 : 0) : -1;
+      at[u] = in_tile ? (col * PITCH + row) | (row < valid ? 1 << 30 : 0) : -1;
       row += dq; col += dr;
       if (col >= D) { col -= D; ++row; }
     }
 #pragma unroll
     for (int u = 0; u < MLP_STAGE; ++u) {
       if (at[u] >= 0) {
-        if (copy && (at[u] >> 30)) copy[(size_t)b0 * D + e0 + 64 * u] = v[u];
+        if (copy && (at[u] >> 30)) copy[(size_t)b0 * D + e0 + LANES * u] = v[u];
         img[at[u] & 0xFFFFF] = NORM ? pob_obsnorm_apply(v[u], mu[u], sc[u], clip) : v[u];
       }
     }
@@ -179,6 +182,153 @@ __global__ __launch_bounds__(64) void k_mlp_forward(const MlpDesc d, const int s
   const float *out = mlp_tile_forward<NORM>(d, imgA, imgB, B, b0, x, theta, nullptr, norm, clip, lane);
   const int valid = B - b0 < MLP_ROWS ? B - b0 : MLP_ROWS;
   mlp_tile_store(y, out, 0, d.sizes[d.n_layers], b0, valid, lane);
+}
+
+// ============================================================================ wide forward
+// k_mlp_forward_wide: the same networks and the same bits as k_mlp_forward, laid out for wide
+// layers over many rows (the critic's [obs -> 256 x 5 -> 1]; DESIGN.md "Wide forward").  A block of
+// MLPW_WAVES = 4 waves owns MLPW_ROWS = 64 consecutive rows, i.e. MLPW_SUB = 2 row sub-tiles of 32.
+// Their activations are ONE LDS image [feature][row] of 256 features at pitch 65 floats (odd: the
+// row-major staging, where consecutive lanes walk features, and the operand reads, where they walk
+// rows, both touch 32 different banks), 66 560 B: two blocks, eight waves, two per SIMD on a CU.
+// The waves split a layer's OUTPUT tiles: wave w holds tiles w and w + 4 (32 (w + 4 i)), each for
+// both row sub-tiles, so a k-step is two global loads of a weight fragment (still W[k][col] of the
+// caller's theta, never copied) and two LDS reads feeding four MFMAs into four accumulators: per
+// MFMA a quarter of the one-wave kernel's LDS reads and half its global loads, and theta is read
+// from L2 once per 64 rows, not once per 32.  Operands are loaded one chunk of MLPW_KUNROLL k-steps
+// ahead of the chunk whose MFMAs run (two register images).  A layer with so few output tiles
+// that tiles x sub-tiles <= waves (the final 256 -> 1) gives each (tile, sub-tile) pair to a wave
+// of its own.  The layer is rewritten in place: every wave has read every k of the image before
+// it holds its outputs, so the block barriers once between the last read and the first write and
+// once after the write.  Per output element the chain is mlp_chain's: bias, then the k-steps of
+// mlp_kfeat in ascending order.
+#define MLPW_WAVES 4
+#define MLPW_SUB 2
+#define MLPW_ROWS (MLP_ROWS * MLPW_SUB)
+#define MLPW_LANES (64 * MLPW_WAVES)
+#define MLPW_PITCH (MLPW_ROWS + 1)
+#define MLPW_KUNROLL 8
+
+// the operands of k-steps [s0, s0 + MLPW_KUNROLL): tile t's column is col0 + 32 MLPW_WAVES t of
+// W (out columns), sub-tile s starts 32 s rows into src; a k-step past the layer's gives zeros
+template <int NT, int NS>
+POB_MLP_D void mlpw_operands(float (&a)[2][MLPW_KUNROLL], float (&b)[MLPW_SUB][MLPW_KUNROLL], const float *src,
+                             const float *W, const int out, const int col0, const int in, const int s0, const int lane) {
+  // every load is issued by every lane, from an address clamped into the layer, and a value from
+  // past it replaced by 0 afterwards: no branch between the loads, so all of a chunk's are in flight
+  // together (32-bit offsets from the uniform W and src: at most 256 x 256 floats)
+  const int j = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int u = 0; u < MLPW_KUNROLL; ++u) {
+    const int k = mlp_kfeat(s0 + u, h);
+    const bool kok = k < in;
+    const unsigned kc = kok ? k : in - 1;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const int col = col0 + 32 * MLPW_WAVES * t;
+      const bool cok = col < out;
+      const float w = W[kc * (unsigned)out + (unsigned)(cok ? col : out - 1)];
+      a[t][u] = (kok && cok) ? w : 0.0f;
+    }
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      const float v = src[kc * MLPW_PITCH + 32 * s + j];
+      b[s][u] = kok ? v : 0.0f;
+    }
+  }
+}
+
+template <int NT, int NS>
+POB_MLP_D void mlpw_mfmas(mlp_f32x16 (&acc)[2][MLPW_SUB], const float (&a)[2][MLPW_KUNROLL],
+                          const float (&b)[MLPW_SUB][MLPW_KUNROLL], const int s0, const int ks) {
+  if (s0 + MLPW_KUNROLL <= ks) {  // a whole chunk: no branch between its MFMAs
+#pragma unroll
+    for (int u = 0; u < MLPW_KUNROLL; ++u)
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int s = 0; s < NS; ++s) acc[t][s] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t][u], b[s][u], acc[t][s], 0, 0, 0);
+    return;
+  }
+#pragma unroll
+  for (int u = 0; u < MLPW_KUNROLL; ++u)
+    if (s0 + u < ks) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int s = 0; s < NS; ++s) acc[t][s] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t][u], b[s][u], acc[t][s], 0, 0, 0);
+    }
+}
+
+// NT output tiles x NS row sub-tiles of one layer: acc[t][s] += the chain over the `in` features
+template <int NT, int NS>
+POB_MLP_D void mlpw_chain(mlp_f32x16 (&acc)[2][MLPW_SUB], const float *src, const float *W, const int out, const int col0,
+                          const int in, const int lane) {
+  const int ks = mlp_ksteps(in);
+  float a0[2][MLPW_KUNROLL], b0[MLPW_SUB][MLPW_KUNROLL], a1[2][MLPW_KUNROLL], b1[MLPW_SUB][MLPW_KUNROLL];
+  mlpw_operands<NT, NS>(a0, b0, src, W, out, col0, in, 0, lane);
+  for (int s0 = 0; s0 < ks; s0 += 2 * MLPW_KUNROLL) {
+    mlpw_operands<NT, NS>(a1, b1, src, W, out, col0, in, s0 + MLPW_KUNROLL, lane);
+    mlpw_mfmas<NT, NS>(acc, a0, b0, s0, ks);
+    mlpw_operands<NT, NS>(a0, b0, src, W, out, col0, in, s0 + 2 * MLPW_KUNROLL, lane);
+    mlpw_mfmas<NT, NS>(acc, a1, b1, s0 + MLPW_KUNROLL, ks);
+  }
+}
+
+// one layer, the image's first `in` features -> its first `out` features, by the block's four waves
+POB_MLP_D void mlpw_layer(float *img, const float *W, const float *bias, const int in, const int out, const bool activate,
+                          const int act, const int lane, const int wave) {
+  const int j = lane & 31, h = lane >> 5;
+  const int n_tiles = (out + 31) >> 5;
+  const bool split = n_tiles * MLPW_SUB <= MLPW_WAVES;  // a wave per (tile, sub-tile) pair
+  const int tile0 = split ? wave / MLPW_SUB : wave, sub0 = split ? wave % MLPW_SUB : 0;
+  const int nt = tile0 >= n_tiles ? 0 : (!split && wave + MLPW_WAVES < n_tiles ? 2 : 1);  // tiles this wave holds
+  const int ns = split ? 1 : MLPW_SUB;
+  const int ot = 32 * tile0;
+  mlp_f32x16 acc[2][MLPW_SUB];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    mlp_acc_bias(acc[t][0], bias, ot + 32 * MLPW_WAVES * t, out, h);
+#pragma unroll
+    for (int s = 1; s < MLPW_SUB; ++s) acc[t][s] = acc[t][0];
+  }
+  const float *src = img + 32 * sub0;
+  if (nt == 2) mlpw_chain<2, MLPW_SUB>(acc, src, W, out, ot + j, in, lane);
+  else if (nt == 1 && !split) mlpw_chain<1, MLPW_SUB>(acc, src, W, out, ot + j, in, lane);
+  else if (nt == 1) mlpw_chain<1, 1>(acc, src, W, out, ot + j, in, lane);
+  __syncthreads();  // every wave has read every k: the image may be rewritten
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int s = 0; s < MLPW_SUB; ++s)
+      if (t < nt && s < ns) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int i = ot + 32 * MLPW_WAVES * t + mlp_acc_row(r, h);
+          if (i < out) img[i * MLPW_PITCH + 32 * (sub0 + s) + j] = activate ? mlp_activate(act, acc[t][s][r]) : acc[t][s][r];
+        }
+      }
+  __syncthreads();
+}
+
+template <bool NORM>
+__global__ __launch_bounds__(MLPW_LANES, 2) __attribute__((target("no-packed-fp32-ops"))) void k_mlp_forward_wide(const MlpDesc d, const int B, const float *x,
+                                                                 const float *theta, float *y, const float *norm,
+                                                                 const float clip) {
+  __shared__ float img[POB_MLP_MAX_WIDTH * MLPW_PITCH];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int b0 = blockIdx.x * MLPW_ROWS;
+  const int valid = B - b0 < MLPW_ROWS ? B - b0 : MLPW_ROWS;
+  mlp_tile_load<NORM, MLPW_ROWS, MLPW_LANES, MLPW_PITCH>(img, x, d.sizes[0], b0, valid, nullptr, nullptr, norm, clip, tid);
+  __syncthreads();
+  const float *W = theta;
+  for (int l = 0; l < d.n_layers; ++l) {
+    const int in = d.sizes[l], out = d.sizes[l + 1];
+    const float *bias = W + (size_t)in * out;
+    mlpw_layer(img, W, bias, in, out, l != d.n_layers - 1 || d.act_final, d.act, lane, wave);
+    W = bias + out;
+  }
+  mlp_tile_store<MLPW_ROWS, MLPW_LANES, MLPW_PITCH>(y, img, 0, d.sizes[d.n_layers], b0, valid, tid);
 }
 
 // The tanh-normal head of one tile: L holds the logits (2 A features), T (A features, another
@@ -457,6 +607,22 @@ int pob_mlp_forward_norm(const pob_mlp *m, int B, const float *x, const float *t
 
 int pob_mlp_forward(const pob_mlp *m, int B, const float *x, const float *theta, float *y, void *stream) {
   return pob_mlp_forward_norm(m, B, x, theta, y, nullptr, 0.0f, stream);
+}
+
+int pob_mlp_forward_wide_norm(const pob_mlp *m, int B, const float *x, const float *theta, float *y, const float *norm,
+                              float norm_clip, void *stream) {
+  if (!m) return pob_fail_msg(POB_EINVAL, "mlp is NULL");
+  if (B < 1) return pob_fail_msg(POB_EINVAL, "mlp: batch size must be positive");
+  if (!x || !theta || !y) return pob_fail_msg(POB_EINVAL, "mlp: NULL argument");
+  const dim3 grid((unsigned)(((long long)B + MLPW_ROWS - 1) / MLPW_ROWS));
+  hipStream_t st = (hipStream_t)stream;
+  if (norm) hipLaunchKernelGGL(k_mlp_forward_wide<true>, grid, dim3(MLPW_LANES), 0, st, m->d, B, x, theta, y, norm, norm_clip);
+  else hipLaunchKernelGGL(k_mlp_forward_wide<false>, grid, dim3(MLPW_LANES), 0, st, m->d, B, x, theta, y, norm, norm_clip);
+  return mlp_hip_check(hipGetLastError(), "k_mlp_forward_wide launch");
+}
+
+int pob_mlp_forward_wide(const pob_mlp *m, int B, const float *x, const float *theta, float *y, void *stream) {
+  return pob_mlp_forward_wide_norm(m, B, x, theta, y, nullptr, 0.0f, stream);
 }
 
 int pob_policy_act_norm(const pob_mlp *m, int B, int total, int first, const float *obs, const float *theta,

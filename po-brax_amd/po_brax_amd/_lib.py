@@ -77,7 +77,9 @@ EXPORTS = (
     "pob_gru_sequence_saved_bytes", "pob_gru_sequence_forward_train", "pob_gru_sequence_backward_workspace_bytes",
     "pob_gru_sequence_backward", "pob_gru_sequence_forward",
     "pob_adam_step",
+    "pob_mlp_forward_wide", "pob_mlp_forward_wide_norm",
 )
+MLP_WIDE_ROWS = 64  # MLPW_ROWS: the rows a block of k_mlp_forward_wide owns
 
 
 class PobError(RuntimeError):
@@ -134,7 +136,8 @@ def _load():
     lib.pob_obsnorm_accumulate.argtypes = [_VP, C.c_longlong, C.c_int, _VP, _VP, _VP, _VP]
     lib.pob_obsnorm_update.argtypes = [_VP, _VP, C.c_int, _VP, C.c_int, C.c_longlong, _VP]
     # the _norm twins: the plain argument list, then norm (3, D), norm_clip, stream
-    for name in ("pob_mlp_forward", "pob_policy_act", "pob_gru_forward", "pob_gru_policy_act"):
+    lib.pob_mlp_forward_wide.argtypes = lib.pob_mlp_forward.argtypes
+    for name in ("pob_mlp_forward", "pob_mlp_forward_wide", "pob_policy_act", "pob_gru_forward", "pob_gru_policy_act"):
         plain = getattr(lib, name).argtypes
         getattr(lib, name + "_norm").argtypes = list(plain[:-1]) + [_VP, C.c_float, _VP]
     # T, B, truncation, second, done_input, reward, reward_scale, values, bootstrap, lambda, discount, vs, adv, stream

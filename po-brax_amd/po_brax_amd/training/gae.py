@@ -23,7 +23,7 @@ import torch
 from .. import _lib
 from .._lib import check, lib, ptr
 from . import normalization as _normalization
-from .networks import FeedForwardModel, Params, RecurrentModel, RecurrentParams
+from .networks import FeedForwardModel, Params, RecurrentModel, RecurrentParams, forward_entry
 
 
 def _gae_torch(truncation, termination, rewards, values, bootstrap_value, lambda_, discount, reward_scaling, vs, adv):
@@ -112,11 +112,14 @@ class ValueFunction:
     """The critic of an actor rollout: a ``make_model`` network whose last width is 1 (the value
     half of ``make_models``).  ``values_into(obs_rows, out)`` is ONE ``pob_mlp_forward_norm``
     launch over (N, D) rows into an (N,) buffer: no allocation, no host sync, capture-safe.
+    ``kernel="resident"`` makes it ``pob_mlp_forward_wide_norm`` (``networks.forward_entry``: the
+    same values, the kernel laid out for a wide network over a whole trajectory's rows).
     ``params.theta`` is read in place at launch time, so an optimiser step between replays is seen
     by a captured graph; so is the table of ``normalizer`` (a
     ``normalization.ObservationNormalizer`` of width ``obs_size``; the policy's, usually)."""
 
-    def __init__(self, model: FeedForwardModel, params: Params, normalizer=None):
+    def __init__(self, model: FeedForwardModel, params: Params, normalizer=None, kernel: str = "tile"):
+        self._forward = forward_entry(kernel, norm=True)
         if model.mlp is None or model.layer_sizes is None:
             raise ValueError("model must come from make_model")
         if model.layer_sizes[-1] != 1:
@@ -143,9 +146,9 @@ class ValueFunction:
         if not (tuple(out.shape) == (N,) and out.dtype == torch.float32 and out.is_contiguous() and out.device == dev):
             raise ValueError(f"out must be a contiguous float32 tensor ({N},) on {dev}")
         norm = self.normalizer
-        check(lib.pob_mlp_forward_norm(self.model.mlp.handle, N, ptr(obs_rows), ptr(self.theta), ptr(out),
-                                       None if norm is None else ptr(norm.table), 0.0 if norm is None else norm.clip,
-                                       _lib.stream_handle(dev)))
+        check(self._forward(self.model.mlp.handle, N, ptr(obs_rows), ptr(self.theta), ptr(out),
+                            None if norm is None else ptr(norm.table), 0.0 if norm is None else norm.clip,
+                            _lib.stream_handle(dev)))
         return out
 
     def __call__(self, obs: torch.Tensor) -> torch.Tensor:

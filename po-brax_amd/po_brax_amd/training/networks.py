@@ -171,13 +171,26 @@ def _forward_torch(sizes, act: int, theta_or_params, x: torch.Tensor) -> torch.T
     return h
 
 
+FORWARD_KERNELS = {"tile": "pob_mlp_forward", "resident": "pob_mlp_forward_wide"}
+
+
+def forward_entry(kernel: str, norm: bool = False):
+    """The fused forward's entry point: ``"tile"`` (one wave per 32 rows: the actor's widths) or
+    ``"resident"`` (four waves per 64 rows, a weight fragment used for both row sub-tiles: wide
+    layers over many rows; DESIGN.md "Wide forward").  The two give the same bits."""
+    if kernel not in FORWARD_KERNELS:
+        raise ValueError(f"kernel must be one of {sorted(FORWARD_KERNELS)}, got {kernel!r}")
+    return getattr(lib, FORWARD_KERNELS[kernel] + ("_norm" if norm else ""))
+
+
 def make_model(layer_sizes: Sequence[int], obs_size: int, activation: Any = "swish",
                spectral_norm: bool = False) -> FeedForwardModel:
     """An MLP ``obs_size -> layer_sizes[0] -> .. -> layer_sizes[-1]`` with ``activation`` after
     every layer but the last.  ``model.init(key)`` returns ``Params`` (on the key's device):
     kernels lecun-uniform U(-sqrt(3 / in), sqrt(3 / in)) drawn through the jumpy uniform, one
-    ``key, sub = split(key)`` per layer; biases zero.  ``model.apply(params, x)``: x (..., obs_size)
-    -> (..., layer_sizes[-1])."""
+    ``key, sub = split(key)`` per layer; biases zero.  ``model.apply(params, x, kernel="tile")``:
+    x (..., obs_size) -> (..., layer_sizes[-1]); ``kernel`` picks the fused forward
+    (``forward_entry``) where one runs, and nothing where the torch ops do."""
     if spectral_norm:
         raise NotImplementedError("spectral_norm: brax's SNDense is not part of this engine (DESIGN.md "
                                   "\"Policy networks\")")
@@ -201,7 +214,8 @@ def make_model(layer_sizes: Sequence[int], obs_size: int, activation: Any = "swi
             parts += [w, torch.zeros(n_out, dtype=torch.float32, device=dev)]
         return Params(torch.cat(parts).contiguous(), sizes)
 
-    def apply(params, x: torch.Tensor) -> torch.Tensor:
+    def apply(params, x: torch.Tensor, kernel: str = "tile") -> torch.Tensor:
+        forward = forward_entry(kernel)
         theta = getattr(params, "theta", None)
         need_grad = torch.is_grad_enabled() and (x.requires_grad or (
             theta.requires_grad if theta is not None else any(t.requires_grad for p in params.values() for t in p.values())))
@@ -216,8 +230,7 @@ def make_model(layer_sizes: Sequence[int], obs_size: int, activation: Any = "swi
         x2 = x.detach().reshape(-1, sizes[0]).contiguous()
         y = torch.empty((x2.shape[0], sizes[-1]), dtype=torch.float32, device=x.device)
         if x2.shape[0]:
-            check(lib.pob_mlp_forward(mlp.handle, x2.shape[0], ptr(x2), ptr(theta.detach()), ptr(y),
-                                      _lib.stream_handle(x.device)))
+            check(forward(mlp.handle, x2.shape[0], ptr(x2), ptr(theta.detach()), ptr(y), _lib.stream_handle(x.device)))
         return y.reshape(*x.shape[:-1], sizes[-1])
 
     class _NativeMLP(torch.autograd.Function):
