@@ -358,6 +358,15 @@ int pob_mlp_forward_train(const pob_mlp *mlp, long long M, const float *x, const
 int pob_mlp_backward_workspace_bytes(const pob_mlp *mlp, long long M, long long *bytes);
 int pob_mlp_backward(const pob_mlp *mlp, long long M, const float *x, const float *theta, const float *saved,
                      const float *dy, float *dtheta, float *dx /* may be NULL */, void *workspace, void *stream);
+/* The same two passes through kernels laid out for wide layers over many rows (the value network's
+ * minibatch; DESIGN.md "Wide training pass"): four waves share 64 rows, the training forward splits
+ * each layer's output columns and the delta pass its input columns among them.  The same arguments,
+ * checks, saved / workspace sizes (the two *_bytes calls above serve both) and error contract, every
+ * network pob_mlp_create accepts, and the same bits in y, saved, dtheta and dx for every M. */
+int pob_mlp_forward_train_wide(const pob_mlp *mlp, long long M, const float *x, const float *theta, float *y,
+                               float *saved, void *stream);
+int pob_mlp_backward_wide(const pob_mlp *mlp, long long M, const float *x, const float *theta, const float *saved,
+                          const float *dy, float *dtheta, float *dx /* may be NULL */, void *workspace, void *stream);
 
 /* ---- Recurrent backward (ABI v8, additive): the training forward of a pob_gru over a window of T
  * steps and its truncated backward pass through time; gru_sequence_forward_train_ref /

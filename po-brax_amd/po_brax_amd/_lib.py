@@ -78,6 +78,7 @@ EXPORTS = (
     "pob_gru_sequence_backward", "pob_gru_sequence_forward",
     "pob_adam_step",
     "pob_mlp_forward_wide", "pob_mlp_forward_wide_norm",
+    "pob_mlp_forward_train_wide", "pob_mlp_backward_wide",
 )
 MLP_WIDE_ROWS = 64  # MLPW_ROWS: the rows a block of k_mlp_forward_wide owns
 
@@ -154,6 +155,8 @@ def _load():
     lib.pob_mlp_forward_train.argtypes = [_VP, C.c_longlong, _VP, _VP, _VP, _VP, _VP]
     # mlp, M, x, theta, saved, dy, dtheta, dx, workspace, stream
     lib.pob_mlp_backward.argtypes = [_VP, C.c_longlong, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]
+    lib.pob_mlp_forward_train_wide.argtypes = lib.pob_mlp_forward_train.argtypes
+    lib.pob_mlp_backward_wide.argtypes = lib.pob_mlp_backward.argtypes
     lib.pob_gru_sequence_saved_bytes.argtypes = [_VP, C.c_int, C.c_longlong, C.POINTER(C.c_longlong)]
     lib.pob_gru_sequence_backward_workspace_bytes.argtypes = [_VP, C.c_int, C.c_longlong, C.POINTER(C.c_longlong)]
     # gru, T, M, B, obs, idx, h0, reset, theta, y, h_last, saved, norm, norm_clip, stream

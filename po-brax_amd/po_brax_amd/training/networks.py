@@ -172,6 +172,9 @@ def _forward_torch(sizes, act: int, theta_or_params, x: torch.Tensor) -> torch.T
 
 
 FORWARD_KERNELS = {"tile": "pob_mlp_forward", "resident": "pob_mlp_forward_wide"}
+# the training pass under the same names: (forward with the pre-activations kept, backward)
+TRAIN_KERNELS = {"tile": ("pob_mlp_forward_train", "pob_mlp_backward"),
+                 "resident": ("pob_mlp_forward_train_wide", "pob_mlp_backward_wide")}
 
 
 def forward_entry(kernel: str, norm: bool = False):
@@ -181,6 +184,14 @@ def forward_entry(kernel: str, norm: bool = False):
     if kernel not in FORWARD_KERNELS:
         raise ValueError(f"kernel must be one of {sorted(FORWARD_KERNELS)}, got {kernel!r}")
     return getattr(lib, FORWARD_KERNELS[kernel] + ("_norm" if norm else ""))
+
+
+def train_entries(kernel: str):
+    """The training pass's two entry points under ``forward_entry``'s names: ``"tile"`` (one wave per 32
+    rows) or ``"resident"`` (four waves per 64 rows: DESIGN.md "Wide training pass").  The same bits."""
+    if kernel not in TRAIN_KERNELS:
+        raise ValueError(f"kernel must be one of {sorted(TRAIN_KERNELS)}, got {kernel!r}")
+    return tuple(getattr(lib, name) for name in TRAIN_KERNELS[kernel])
 
 
 def make_model(layer_sizes: Sequence[int], obs_size: int, activation: Any = "swish",
@@ -234,18 +245,19 @@ def make_model(layer_sizes: Sequence[int], obs_size: int, activation: Any = "swi
         return y.reshape(*x.shape[:-1], sizes[-1])
 
     class _NativeMLP(torch.autograd.Function):
-        """theta (contiguous float32 CUDA), x2 (M, sizes[0]) contiguous float32 CUDA, M >= 1."""
+        """theta (contiguous float32 CUDA), x2 (M, sizes[0]) contiguous float32 CUDA, M >= 1; entries:
+        ``train_entries``' pair."""
 
         @staticmethod
-        def forward(ctx, theta, x2):
+        def forward(ctx, theta, x2, entries):
             M, dev = int(x2.shape[0]), x2.device
             need = C.c_longlong()
             check(lib.pob_mlp_saved_bytes(mlp.handle, M, C.byref(need)))
             saved = torch.empty(need.value // 4, dtype=torch.float32, device=dev)
             y = torch.empty((M, sizes[-1]), dtype=torch.float32, device=dev)
-            check(lib.pob_mlp_forward_train(mlp.handle, M, ptr(x2), ptr(theta), ptr(y), ptr(saved),
-                                            _lib.stream_handle(dev)))
+            check(entries[0](mlp.handle, M, ptr(x2), ptr(theta), ptr(y), ptr(saved), _lib.stream_handle(dev)))
             ctx.save_for_backward(theta, x2, saved)
+            ctx.backward_entry = entries[1]
             return y
 
         @staticmethod
@@ -259,22 +271,25 @@ def make_model(layer_sizes: Sequence[int], obs_size: int, activation: Any = "swi
             workspace = torch.empty(need.value // 8, dtype=torch.float64, device=dev)
             dtheta = torch.empty_like(theta)
             dx = torch.empty_like(x2) if ctx.needs_input_grad[1] else None
-            check(lib.pob_mlp_backward(mlp.handle, M, ptr(x2), ptr(theta), ptr(saved), ptr(dy), ptr(dtheta), ptr(dx),
-                                       ptr(workspace), _lib.stream_handle(dev)))
-            return (dtheta if ctx.needs_input_grad[0] else None), dx
+            check(ctx.backward_entry(mlp.handle, M, ptr(x2), ptr(theta), ptr(saved), ptr(dy), ptr(dtheta), ptr(dx),
+                                     ptr(workspace), _lib.stream_handle(dev)))
+            return (dtheta if ctx.needs_input_grad[0] else None), dx, None
 
-    def apply_native(params, x: torch.Tensor) -> torch.Tensor:
+    def apply_native(params, x: torch.Tensor, kernel: str = "tile") -> torch.Tensor:
         """``apply`` whose backward pass runs in the engine as well: for a ``Params`` (or a namespace
         with ``.theta``) whose ``theta`` is a contiguous float32 CUDA tensor and a float32 CUDA ``x``,
         the forward is ``pob_mlp_forward_train`` (``apply``'s fused bits, the pre-activations kept)
         and the backward ``pob_mlp_backward`` (``theta.grad``, and ``x.grad`` only when ``x`` requires
-        it).  Anything else (the CPU, other dtypes, the dict-of-views form) takes the torch ops under
-        autograd; when no gradient is needed this is ``apply``."""
+        it); ``kernel="resident"`` makes them ``pob_mlp_forward_train_wide`` and ``pob_mlp_backward_wide``
+        (``train_entries``: the same bits, laid out for a wide network over many rows).  Anything else
+        (the CPU, other dtypes, the dict-of-views form) takes the torch ops under autograd, where
+        ``kernel`` selects nothing; when no gradient is needed this is ``apply``."""
+        entries = train_entries(kernel)
         theta = getattr(params, "theta", None)
         need_grad = torch.is_grad_enabled() and (x.requires_grad or (
             theta.requires_grad if theta is not None else any(t.requires_grad for p in params.values() for t in p.values())))
         if not need_grad:
-            return apply(params, x)
+            return apply(params, x, kernel)
         native = (theta is not None and x.is_cuda and x.dtype == torch.float32 and theta.is_cuda
                   and theta.dtype == torch.float32 and theta.is_contiguous() and x.numel() > 0)
         if not native:
@@ -283,7 +298,7 @@ def make_model(layer_sizes: Sequence[int], obs_size: int, activation: Any = "swi
             raise ValueError(f"theta has {theta.numel()} elements, the network {mlp.param_count}")
         if x.shape[-1] != sizes[0]:
             raise ValueError(f"x must be (..., {sizes[0]})")
-        y = _NativeMLP.apply(theta, x.reshape(-1, sizes[0]).contiguous())
+        y = _NativeMLP.apply(theta, x.reshape(-1, sizes[0]).contiguous(), entries)
         return y.reshape(*x.shape[:-1], sizes[-1])
 
     return FeedForwardModel(init=init, apply=apply, layer_sizes=sizes, activation=act, mlp=mlp,

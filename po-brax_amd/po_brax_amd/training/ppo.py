@@ -28,6 +28,7 @@ through ``model.apply_sequence`` / ``apply_sequence_native`` (DESIGN.md "Recurre
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 import types
 from typing import Dict, Optional, Tuple
@@ -386,6 +387,16 @@ class _DeviceLearner:
         return torch.randperm(n, device=dev, generator=self._generator).to(torch.int32)
 
 
+_BACKWARDS = ("torch", "native", "resident")
+
+
+def _apply_under_grad(model, backward: str):
+    """A feed-forward model's forward-with-grad for one of ``_BACKWARDS``."""
+    if backward == "resident":
+        return functools.partial(model.apply_native, kernel="resident")
+    return model.apply_native if backward == "native" else model.apply
+
+
 class PPOLearner(_DeviceLearner):
     """The minibatch loop of brax v1 PPO over one replay of an ``ActorRollout(..., critic=value_fn)``:
 
@@ -404,11 +415,16 @@ class PPOLearner(_DeviceLearner):
 
     ``backward`` chooses each network's forward-with-grad and backward pass: ``"torch"`` (the default:
     the torch-op ``apply`` under autograd), ``"native"`` (``model.apply_native``: ``pob_mlp_forward_train``
-    and ``pob_mlp_backward``, the fused forward's bits and a fixed summation order), or a pair
-    ``(policy, value)`` of those.  Measured on an MI355X at 40 960 rows a minibatch (DESIGN.md "MLP
-    backward"): the policy network ``[32] * 4`` should use ``"native"`` (4.0 x faster than the torch
-    ops), the 256-wide value network ``"torch"`` (the native pass is 2.4 x slower than the vendor
-    GEMMs), i.e. ``backward=("native", "torch")``: one update in 78 ms against 108 ms for the default.
+    and ``pob_mlp_backward``, the fused forward's bits and a fixed summation order), ``"resident"``
+    (``model.apply_native(kernel="resident")``: ``"native"``'s bits from the four-wave kernels for wide
+    layers, ``pob_mlp_forward_train_wide`` and ``pob_mlp_backward_wide``), or a pair ``(policy, value)`` of
+    those.  Measured on an MI355X at 40 960 rows a minibatch (DESIGN.md "MLP backward" and "Wide training
+    pass"): the policy network ``[32] * 4`` should use ``"native"`` (4.6 x faster than the torch ops; the
+    four-wave kernels gain nothing at width 32).  For the 256-wide value network ``"native"`` is 2.4 x
+    slower than the vendor GEMMs, ``"resident"`` level with them (1.87 ms against 1.86 ms, inside each
+    other's range): ``backward=("native", "torch")`` remains the setting to use for speed (one update in
+    77.3 ms against 106.6 ms for the default), and ``("native", "resident")`` costs the same to within
+    0.4 % (77.6 ms) where the value gradient is wanted in the engine's fixed summation order.
 
     ``optimizer``: ``"torch"`` (the default: ``torch.optim.Adam``) or ``"fused"`` (``training.optim.FusedAdam``:
     both parameter vectors in one launch, the step count on the device).  ``permutation``: ``"torch"`` (the
@@ -425,8 +441,9 @@ class PPOLearner(_DeviceLearner):
                  ppo_epsilon: float = 0.3, num_minibatches: int = 32, num_update_epochs: int = 4, key=None,
                  backward="torch", optimizer: str = "torch", permutation: str = "torch"):
         pair = (backward, backward) if isinstance(backward, str) else backward
-        if not (isinstance(pair, (tuple, list)) and len(pair) == 2 and all(b in ("torch", "native") for b in pair)):
-            raise ValueError(f"backward must be 'torch', 'native' or a (policy, value) pair of those, got {backward!r}")
+        if not (isinstance(pair, (tuple, list)) and len(pair) == 2 and all(b in _BACKWARDS for b in pair)):
+            raise ValueError(f"backward must be 'torch', 'native', 'resident' or a (policy, value) pair of those, "
+                             f"got {backward!r}")
         self.backward = tuple(pair)
         if not isinstance(policy, _networks.NormalTanhPolicy):
             raise TypeError("policy must be a training.networks.NormalTanhPolicy (the feed-forward actor)")
@@ -459,8 +476,7 @@ class PPOLearner(_DeviceLearner):
         norm, v_norm = self.policy.normalizer, self.value_fn.normalizer
         p_params = types.SimpleNamespace(theta=self._theta[0])
         v_params = types.SimpleNamespace(theta=self._theta[1])
-        p_apply, v_apply = (m.apply_native if b == "native" else m.apply
-                            for m, b in zip((self.policy.model, self.value_fn.model), self.backward))
+        p_apply, v_apply = (_apply_under_grad(m, b) for m, b in zip((self.policy.model, self.value_fn.model), self.backward))
         metrics = None
         for _ in range(self.num_update_epochs):
             perm = self._draw_permutation(N, obs.device)
@@ -504,13 +520,14 @@ class RecurrentPPOLearner(_DeviceLearner):
     ``model.apply_sequence`` under autograd on the gathered, normalised rows (CPU tensors too) and
     ``"native"`` is ``model.apply_sequence_native`` (``pob_gru_sequence_forward_train`` /
     ``pob_gru_sequence_backward``, the trajectory read in place: DESIGN.md "Recurrent backward"); for
-    a feed-forward value network they are ``PPOLearner``'s.  The default (``"auto"``) is then ``("native",
-    "torch")``.  Measured on an
+    a feed-forward value network they are ``PPOLearner``'s, ``"resident"`` among them (the value element
+    only).  The default (``"auto"``) is then ``("native", "torch")``.  Measured on an
     MI355X (DESIGN.md "Recurrent backward"): a window of T = 20 steps of 2 048 envs, forward with grad plus
     backward, takes 3.09 ms natively against 12.3 ms in torch ops (114 -> GRU 64 -> 16; 2.35 against 12.4 ms
     at 30 columns), and one update of 32 such minibatches 172 ms against 403 ms for ``"torch"`` and 254 ms
-    for ``"native"``; the value half stays ``"torch"`` (DESIGN.md "MLP backward": the vendor GEMMs win at
-    width 256).
+    for ``"native"``; the value half stays ``"torch"`` (DESIGN.md "Wide training pass": at width 256 the
+    vendor GEMMs beat ``"native"`` 2.4 x and are level with ``"resident"``, which is the one to choose for
+    the engine's fixed summation order).
 
     ``value_fn`` may be a ``RecurrentValueFunction`` (DESIGN.md "Recurrent critic"): the value network is
     then unrolled over the same windows as the policy, from ``roll.value_hidden0`` (the post-reset state
@@ -536,9 +553,11 @@ class RecurrentPPOLearner(_DeviceLearner):
         if isinstance(backward, str) and backward == "auto":
             backward = ("native", "native") if self.recurrent_critic else ("native", "torch")
         pair = (backward, backward) if isinstance(backward, str) else backward
-        if not (isinstance(pair, (tuple, list)) and len(pair) == 2 and all(b in ("torch", "native") for b in pair)):
-            raise ValueError("backward must be 'auto', 'torch', 'native' or a (policy, value) pair of the last two, "
-                             f"got {backward!r}")
+        ok = isinstance(pair, (tuple, list)) and len(pair) == 2 and all(b in _BACKWARDS for b in pair)
+        # "resident" names a feed-forward network's kernels: the value half, and only of a ValueFunction
+        if not ok or pair[0] == "resident" or (pair[1] == "resident" and self.recurrent_critic):
+            raise ValueError("backward must be 'auto', 'torch', 'native' or a (policy, value) pair of the last two "
+                             f"(value: also 'resident' for a feed-forward ValueFunction), got {backward!r}")
         self.backward = tuple(pair)
         if key is None:
             raise ValueError("key is required (jumpy.random_prngkey)")
@@ -579,7 +598,7 @@ class RecurrentPPOLearner(_DeviceLearner):
         v_h0 = roll.value_hidden0 if self.recurrent_critic else None
         # the native windows read the trajectory in place: no gathered rows when both halves are such
         gathered = not (self.recurrent_critic and self.backward == ("native", "native"))
-        v_apply = None if self.recurrent_critic else (v_model.apply_native if self.backward[1] == "native" else v_model.apply)
+        v_apply = None if self.recurrent_critic else _apply_under_grad(v_model, self.backward[1])
         metrics = None
         for _ in range(self.num_update_epochs):
             perm = self._draw_permutation(B, dev)

@@ -1,20 +1,23 @@
 """mlp_backward_bench.py -- what the networks' forward-with-grad plus backward costs on the device.
 
 For the policy and the value network of make_models(16, 114) at M = 40 960 (one of 32 minibatches of
-HH B = 65 536, T = 20): forward with grad, then backward to theta.grad, two legs alternating call by
+HH B = 65 536, T = 20): forward with grad, then backward to theta.grad, three legs alternating call by
 call in one process, the median of each reported with min .. max:
 
-  native   model.apply_native: pob_mlp_forward_train and pob_mlp_backward (k_mlp_forward_train,
+  resident model.apply_native(kernel="resident"): pob_mlp_forward_train_wide and pob_mlp_backward_wide
+           (k_mlp_forward_train_wide, k_mlp_bwd_delta_wide, then the two kernels below) with their allocations
+  native   model.apply_native (kernel="tile"): pob_mlp_forward_train and pob_mlp_backward (k_mlp_forward_train,
            k_mlp_bwd_delta, k_mlp_bwd_weights, k_mlp_bwd_reduce) with their allocations
   torch    the torch-op model.apply under autograd (addmm / silu and their backward)
 
 then one PPOLearner.update (one epoch, 32 minibatches of 40 960 rows of synthetic rollout buffers)
-under backward = "torch", "native" and ("native", "torch"), alternating the same way (--no-learner
-skips it).  Prints one JSON line.
+under backward = "torch", "native", ("native", "torch") and ("native", "resident"), alternating the same
+way (--no-learner skips it).  Prints one JSON line.
 
     python scripts/mlp_backward_bench.py [--rounds 15] [--out FILE]
 """
 import argparse
+import functools
 import json
 import os
 import statistics
@@ -73,7 +76,8 @@ def bench_network(name, model, M, rounds, warmup):
             fn(params, x).backward(dy)
         return run
 
-    legs = {"native": leg(model.apply_native), "torch": leg(model.apply)}
+    legs = {"resident": leg(functools.partial(model.apply_native, kernel="resident")),
+            "native": leg(model.apply_native), "torch": leg(model.apply)}
     # the legs agree before they are timed
     grads = {}
     for k, fn in legs.items():
@@ -84,9 +88,11 @@ def bench_network(name, model, M, rounds, warmup):
     out = {"network": name, "sizes": list(sizes), "M": M, "gflop": round(flop / 1e9, 2),
            "ms_at_f32_mfma_peak": round(flop / F32_MFMA_PEAK * 1e3, 4),
            "max_abs_grad_difference": float((grads["native"] - grads["torch"]).abs().max()),
+           "resident_grad_equals_native": bool(torch.equal(grads["resident"], grads["native"])),
            "largest_grad": float(grads["torch"].abs().max())}
     out.update(summary(interleaved(legs, rounds, warmup)))
     out["torch_over_native"] = round(out["torch_ms"] / out["native_ms"], 3)
+    out["torch_over_resident"] = round(out["torch_ms"] / out["resident_ms"], 3)
     return out
 
 
@@ -107,7 +113,8 @@ def bench_learner(T, B, rounds, warmup):
     p_model, v_model = networks.make_models(2 * A, D)
     g = torch.Generator(device="cuda").manual_seed(5)
     legs = {}
-    for name, backward in (("torch", "torch"), ("native", "native"), ("native_torch", ("native", "torch"))):
+    for name, backward in (("torch", "torch"), ("native", "native"), ("native_torch", ("native", "torch")),
+                           ("native_resident", ("native", "resident"))):
         policy = networks.NormalTanhPolicy(p_model, p_model.init(jumpy.random_prngkey(5)), jumpy.random_prngkey(6))
         critic = ValueFunction(v_model, v_model.init(jumpy.random_prngkey(9)))
         learner = PPOLearner(policy, critic, learning_rate=1e-5, num_minibatches=32, num_update_epochs=1,
