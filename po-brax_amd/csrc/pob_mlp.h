@@ -1,8 +1,9 @@
 // pob_mlp.h -- the scalar math and the plain-C restatement of the policy-network kernels
-// (pob_mlp.hip: k_mlp_forward, k_policy_act, the recurrent k_gru_forward, k_gru_policy_act, the
-// observation normaliser's k_obsnorm_*, k_gae, k_ppo_* and the training forward / backward pass
-// k_mlp_forward_train, k_mlp_bwd_*, and the recurrent window's k_gru_seq_forward, k_gru_seq_backward,
-// k_gru_bwd_weights, k_gru_seq_infer, and the optimiser's k_adam_step).
+// (pob_mlp.hip: k_mlp_forward, k_policy_act; pob_gru.hip: the recurrent k_gru_forward,
+// k_gru_policy_act; pob_learner.hip: the observation normaliser's k_obsnorm_*, k_gae, k_ppo_* and the
+// optimiser's k_adam_step; pob_mlp_train.hip: the training forward / backward pass k_mlp_forward_train,
+// k_mlp_bwd_*; pob_gru_seq.hip: the recurrent window's k_gru_seq_forward, k_gru_seq_backward,
+// k_gru_bwd_weights, k_gru_seq_infer).
 // Compiled for the device by hipcc and, with POB_MLP_HOST, for the host by g++
 // (tests/host/mlp_host.cpp, gru_host.cpp, obsnorm_host.cpp, gae_host.cpp, ppo_host.cpp,
 // mlp_bwd_host.cpp, gru_bwd_host.cpp, gru_seq_infer_host.cpp, adam_host.cpp); both with -ffp-contract=off.

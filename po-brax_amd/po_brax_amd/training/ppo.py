@@ -351,7 +351,19 @@ class _DeviceLearner:
     """What both learners share of the device-resident update: the optimiser and permutation options
     (DESIGN.md "Learner on the device")."""
 
-    def _init_options(self, key, learning_rate: float, optimizer: str, permutation: str) -> None:
+    def __init__(self, policy, value_fn, backward, learning_rate: float, entropy_cost: float, ppo_epsilon: float,
+                 num_minibatches: int, num_update_epochs: int, key, optimizer: str, permutation: str) -> None:
+        """``policy`` and ``value_fn`` of the subclass's kinds, ``backward`` from ``_backward_pair``."""
+        self.backward = backward
+        if key is None:
+            raise ValueError("key is required (jumpy.random_prngkey)")
+        if int(num_minibatches) < 1 or int(num_update_epochs) < 1:
+            raise ValueError("num_minibatches and num_update_epochs must be positive")
+        if policy.obs_size != value_fn.obs_size or policy.theta.device != value_fn.theta.device:
+            raise ValueError("policy and value_fn must share the observation width and the device")
+        self.policy, self.value_fn = policy, value_fn
+        self.entropy_cost, self.ppo_epsilon = float(entropy_cost), float(ppo_epsilon)
+        self.num_minibatches, self.num_update_epochs = int(num_minibatches), int(num_update_epochs)
         if optimizer not in ("torch", "fused"):
             raise ValueError(f"optimizer must be 'torch' or 'fused', got {optimizer!r}")
         if permutation not in ("torch", "threefry"):
@@ -376,6 +388,22 @@ class _DeviceLearner:
                 self.perm_key = jumpy.random_split_rows(self.key, 3, 2, 1).reshape(2)
             else:
                 self.perm_key = _networks._host_split(words, 3)[2].to(torch.uint32)
+
+    @staticmethod
+    def _backward_pair(backward, allowed, message: str):
+        """``backward`` as a (policy, value) pair of ``_BACKWARDS`` that ``allowed(pair)`` admits."""
+        pair = (backward, backward) if isinstance(backward, str) else backward
+        ok = isinstance(pair, (tuple, list)) and len(pair) == 2 and all(b in _BACKWARDS for b in pair)
+        if not (ok and allowed(pair)):
+            raise ValueError(f"{message}, got {backward!r}")
+        return tuple(pair)
+
+    def _step(self, total: torch.Tensor, metrics) -> Dict[str, torch.Tensor]:
+        """A minibatch's tail: one optimiser step on ``total``; returns its metrics with ``total_loss``."""
+        self.optimizer.zero_grad(set_to_none=True)
+        total.backward()
+        self.optimizer.step()
+        return dict(metrics, total_loss=total.detach())
 
     def _draw_permutation(self, n: int, dev) -> torch.Tensor:
         """One epoch's int32 permutation of n items on ``dev``."""
@@ -440,25 +468,14 @@ class PPOLearner(_DeviceLearner):
     def __init__(self, policy, value_fn, learning_rate: float = 3e-4, entropy_cost: float = 1e-4,
                  ppo_epsilon: float = 0.3, num_minibatches: int = 32, num_update_epochs: int = 4, key=None,
                  backward="torch", optimizer: str = "torch", permutation: str = "torch"):
-        pair = (backward, backward) if isinstance(backward, str) else backward
-        if not (isinstance(pair, (tuple, list)) and len(pair) == 2 and all(b in _BACKWARDS for b in pair)):
-            raise ValueError(f"backward must be 'torch', 'native', 'resident' or a (policy, value) pair of those, "
-                             f"got {backward!r}")
-        self.backward = tuple(pair)
+        pair = self._backward_pair(backward, lambda pair: True,
+                                   "backward must be 'torch', 'native', 'resident' or a (policy, value) pair of those")
         if not isinstance(policy, _networks.NormalTanhPolicy):
             raise TypeError("policy must be a training.networks.NormalTanhPolicy (the feed-forward actor)")
         if not isinstance(value_fn, ValueFunction):
             raise TypeError("value_fn must be a training.ValueFunction")
-        if key is None:
-            raise ValueError("key is required (jumpy.random_prngkey)")
-        if int(num_minibatches) < 1 or int(num_update_epochs) < 1:
-            raise ValueError("num_minibatches and num_update_epochs must be positive")
-        if policy.obs_size != value_fn.obs_size or policy.theta.device != value_fn.theta.device:
-            raise ValueError("policy and value_fn must share the observation width and the device")
-        self.policy, self.value_fn = policy, value_fn
-        self.entropy_cost, self.ppo_epsilon = float(entropy_cost), float(ppo_epsilon)
-        self.num_minibatches, self.num_update_epochs = int(num_minibatches), int(num_update_epochs)
-        self._init_options(key, learning_rate, optimizer, permutation)
+        super().__init__(policy, value_fn, pair, learning_rate, entropy_cost, ppo_epsilon, num_minibatches,
+                         num_update_epochs, key, optimizer, permutation)
 
     def update(self, roll) -> Dict[str, torch.Tensor]:
         """One learning phase over ``roll``'s buffers as the last replay left them; returns the last
@@ -490,10 +507,7 @@ class PPOLearner(_DeviceLearner):
                     values = v_apply(v_params, x_v).reshape(M)
                     total, metrics = ppo_loss(logits, values, raw, logp, adv, vs, self.key, idx=idx,
                                               entropy_cost=self.entropy_cost, ppo_epsilon=self.ppo_epsilon)
-                self.optimizer.zero_grad(set_to_none=True)
-                total.backward()
-                self.optimizer.step()
-                metrics = dict(metrics, total_loss=total.detach())
+                metrics = self._step(total, metrics)
         return metrics
 
 
@@ -552,23 +566,13 @@ class RecurrentPPOLearner(_DeviceLearner):
         self.recurrent_critic = isinstance(value_fn, RecurrentValueFunction)
         if isinstance(backward, str) and backward == "auto":
             backward = ("native", "native") if self.recurrent_critic else ("native", "torch")
-        pair = (backward, backward) if isinstance(backward, str) else backward
-        ok = isinstance(pair, (tuple, list)) and len(pair) == 2 and all(b in _BACKWARDS for b in pair)
         # "resident" names a feed-forward network's kernels: the value half, and only of a ValueFunction
-        if not ok or pair[0] == "resident" or (pair[1] == "resident" and self.recurrent_critic):
-            raise ValueError("backward must be 'auto', 'torch', 'native' or a (policy, value) pair of the last two "
-                             f"(value: also 'resident' for a feed-forward ValueFunction), got {backward!r}")
-        self.backward = tuple(pair)
-        if key is None:
-            raise ValueError("key is required (jumpy.random_prngkey)")
-        if int(num_minibatches) < 1 or int(num_update_epochs) < 1:
-            raise ValueError("num_minibatches and num_update_epochs must be positive")
-        if policy.obs_size != value_fn.obs_size or policy.theta.device != value_fn.theta.device:
-            raise ValueError("policy and value_fn must share the observation width and the device")
-        self.policy, self.value_fn = policy, value_fn
-        self.entropy_cost, self.ppo_epsilon = float(entropy_cost), float(ppo_epsilon)
-        self.num_minibatches, self.num_update_epochs = int(num_minibatches), int(num_update_epochs)
-        self._init_options(key, learning_rate, optimizer, permutation)
+        pair = self._backward_pair(
+            backward, lambda pair: pair[0] != "resident" and not (pair[1] == "resident" and self.recurrent_critic),
+            "backward must be 'auto', 'torch', 'native' or a (policy, value) pair of the last two "
+            "(value: also 'resident' for a feed-forward ValueFunction)")
+        super().__init__(policy, value_fn, pair, learning_rate, entropy_cost, ppo_epsilon, num_minibatches,
+                         num_update_epochs, key, optimizer, permutation)
 
     def update(self, roll) -> Dict[str, torch.Tensor]:
         """One learning phase over ``roll``'s buffers as the last replay left them; returns the last
@@ -627,8 +631,5 @@ class RecurrentPPOLearner(_DeviceLearner):
                                                         reset.index_select(1, j))[0].reshape(T * M)
                     total, metrics = ppo_loss(logits, values, raw, logp, adv, vs, self.key, idx=rows,
                                               entropy_cost=self.entropy_cost, ppo_epsilon=self.ppo_epsilon)
-                self.optimizer.zero_grad(set_to_none=True)
-                total.backward()
-                self.optimizer.step()
-                metrics = dict(metrics, total_loss=total.detach())
+                metrics = self._step(total, metrics)
         return metrics

@@ -5,8 +5,8 @@ set -e
 NAME=$1; shift
 cd "$(dirname "$0")/.."
 mkdir -p build_variants
-CS=po-brax_amd/csrc
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -fno-slp-vectorize \
-  -fPIC -shared -mcode-object-version=5 -Wall -Wno-unused-result "$@" \
-  -o build_variants/.$NAME.tmp $CS/pob_kernels.hip $CS/pob_system.cpp $CS/pob_mlp.hip
+# the sources and the flags are the build's own (__graft_entry__.py)
+SRCS=$(python3 -c "import os, __graft_entry__ as g; print(*[os.path.join(g.CSRC, f) for f in g.HIP_SOURCES])")
+FLAGS=$(python3 -c "import __graft_entry__ as g; print(*g.HIPCC_FLAGS)")
+/opt/rocm/bin/hipcc $FLAGS -shared "$@" -o build_variants/.$NAME.tmp $SRCS
 mv build_variants/.$NAME.tmp build_variants/$NAME.so  # (atomic: a GPU snapshot never sees half a library)

@@ -1,4 +1,4 @@
-"""GPU: the recurrent-actor kernels (csrc/pob_mlp.hip k_gru_forward / k_gru_policy_act) equal
+"""GPU: the recurrent-actor kernels (csrc/pob_gru.hip k_gru_forward / k_gru_policy_act) equal
 their plain-C restatement (csrc/pob_mlp.h gru_forward_ref / gru_policy_ref, built for the host by
 tests/host/gru_host.cpp) bit for bit -- forward, hidden state, reset, actor -- and
 RecurrentActorRollout equals the same loop run eagerly."""

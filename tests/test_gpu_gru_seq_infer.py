@@ -44,7 +44,7 @@ def _cuda(a):
 
 
 def pool_rows(net):
-    """I + 2 H + P0 + P1 by gru_tile_forward's walk (gru_plan of csrc/pob_mlp.hip)."""
+    """I + 2 H + P0 + P1 by gru_tile_forward's walk (gru_plan of csrc/pob_gru_tile.h)."""
     pre, H, post = net
     w, pp = [0, 0], 0
     if len(pre) > 1:

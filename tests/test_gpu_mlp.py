@@ -1,4 +1,4 @@
-"""GPU: the policy-network kernels (csrc/pob_mlp.hip) equal their plain-C restatement
+"""GPU: the policy-network kernels (csrc/pob_mlp.hip, csrc/pob_mlp_tile.h) equal their plain-C restatement
 (csrc/pob_mlp.h, built for the host by tests/host/mlp_host.cpp) bit for bit -- forward and
 tanh-normal actor -- and the rollouts built on them equal the same loop run eagerly."""
 import numpy as np
