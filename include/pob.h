@@ -437,6 +437,26 @@ typedef struct pob_adam_seg {
 int pob_adam_step(const pob_adam_seg *segs, int n_seg, double *state, float lr, float beta1, float beta2, float eps,
                   void *stream);
 
+/* ---- Stable radix sort and the native permutation (ABI v8, additive; DESIGN.md "Native stable radix
+ * sort"): least-significant-digit radix sort of (uint32 key, int32 value) pairs, 8 bits a pass, keys in
+ * UNSIGNED ascending order, equal keys in their input order.  The caller owns the workspace: device
+ * memory of at least pob_sort_workspace_bytes(n) bytes, 4-byte aligned, contents irrelevant before and
+ * after a call.  Arguments are checked before any HIP call (NULL pointers, n outside 1 .. 2^31 - 1, a
+ * short workspace, pointers that are not 4-byte aligned -> POB_EINVAL); no allocation, no
+ * synchronisation, and a launch sequence that depends on n alone.
+ * pob_sort_workspace_bytes: the bytes for n elements, or POB_EINVAL (negative) for n out of range.
+ * pob_sort_pairs_u32: keys_out, vals_out <- the pairs sorted by key; vals == NULL sorts iota(n) (an
+ * argsort), keys_out == NULL stores no keys.  The outputs may be the inputs.
+ * pob_random_permutation: jax.random.permutation(key, n) as jumpy.random_permutation states it: x =
+ * iota(n); permutation_rounds(n) times `key, sub = split(key)` and x sorted stably by
+ * random_bits(sub, (n,)), the splits and the words formed on the device.  key (2 words) is only read;
+ * n = 1 stores 0. */
+long long pob_sort_workspace_bytes(long long n);
+int pob_sort_pairs_u32(const uint32_t *keys, const int32_t *vals, long long n, uint32_t *keys_out, int32_t *vals_out,
+                       void *workspace, long long ws_bytes, void *stream);
+int pob_random_permutation(const uint32_t *key, long long n, int32_t *out, void *workspace, long long ws_bytes,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif

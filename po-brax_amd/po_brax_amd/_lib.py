@@ -79,8 +79,11 @@ EXPORTS = (
     "pob_adam_step",
     "pob_mlp_forward_wide", "pob_mlp_forward_wide_norm",
     "pob_mlp_forward_train_wide", "pob_mlp_backward_wide",
+    "pob_sort_workspace_bytes", "pob_sort_pairs_u32", "pob_random_permutation",
 )
 MLP_WIDE_ROWS = 64  # MLPW_ROWS: the rows a block of k_mlp_forward_wide owns
+SORT_TILE = 2048  # POB_SORT_TILE: the elements a block of the radix sort owns
+SORT_SCAN_CHUNK = 256  # POB_SORT_SCAN_CHUNK: the tiles k_sort_scan takes at a time
 
 
 class PobError(RuntimeError):
@@ -170,10 +173,17 @@ def _load():
                                              _VP, C.c_int, _VP, C.c_float, _VP]
     # segs (host array), n_seg, state, lr, beta1, beta2, eps, stream
     lib.pob_adam_step.argtypes = [C.POINTER(pob_adam_seg), C.c_int, _VP, C.c_float, C.c_float, C.c_float, C.c_float, _VP]
+    lib.pob_sort_workspace_bytes.argtypes = [C.c_longlong]
+    lib.pob_sort_workspace_bytes.restype = C.c_longlong
+    # keys, vals, n, keys_out, vals_out, workspace, ws_bytes, stream
+    lib.pob_sort_pairs_u32.argtypes = [_VP, _VP, C.c_longlong, _VP, _VP, _VP, C.c_longlong, _VP]
+    # key, n, out, workspace, ws_bytes, stream
+    lib.pob_random_permutation.argtypes = [_VP, C.c_longlong, _VP, _VP, C.c_longlong, _VP]
     if lib.pob_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {lib.pob_abi_version()} != {ABI_VERSION}; rebuild it")
     for name in EXPORTS:
-        if name not in ("pob_abi_version", "pob_last_error", "pob_env_destroy", "pob_mlp_destroy", "pob_gru_destroy"):
+        if name not in ("pob_abi_version", "pob_last_error", "pob_env_destroy", "pob_mlp_destroy", "pob_gru_destroy",
+                        "pob_sort_workspace_bytes"):
             getattr(lib, name).restype = C.c_int
     return lib
 

@@ -103,14 +103,69 @@ def permutation_rounds(n: int) -> int:
     return int(math.ceil(3.0 * math.log(max(1, int(n))) / math.log(2 ** 32 - 1)))
 
 
-def random_permutation(key: torch.Tensor, n: int) -> torch.Tensor:
+def sort_workspace_bytes(n: int) -> int:
+    """``pob_sort_workspace_bytes(n)``: the scratch memory the radix sort wants for n elements."""
+    n = int(n)
+    if not 1 <= n < 2 ** 31:
+        raise ValueError(f"n must be in 1 .. 2^31 - 1, got {n}")
+    return int(lib.pob_sort_workspace_bytes(n))
+
+
+def sort_workspace(n: int, device) -> torch.Tensor:
+    """A uint8 tensor of ``sort_workspace_bytes(n)`` on ``device``: what ``stable_argsort`` and
+    ``random_permutation(sort="native")`` take as ``workspace`` for n elements (a larger one serves too)."""
+    return torch.empty(sort_workspace_bytes(n), dtype=torch.uint8, device=device)
+
+
+def _sort_buffers(n: int, device, out, workspace):
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=device)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (n,) or out.device != device or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous int32 tensor of shape ({n},) on {device}")
+    if workspace is None:
+        workspace = sort_workspace(n, device)
+    elif workspace.dtype != torch.uint8 or workspace.device != device or not workspace.is_contiguous():
+        raise ValueError(f"workspace must be a contiguous uint8 tensor on {device}")
+    return out, workspace
+
+
+def stable_argsort(words: torch.Tensor, out=None, workspace=None) -> torch.Tensor:
+    """The stable ascending order of uint32 ``words`` (n,) as int32 (n,): ``out[i]`` is the index of the
+    i-th smallest word, equal words in index order.  On a device tensor this is the engine's radix sort
+    (``pob_sort_pairs_u32`` against iota, DESIGN.md "Native stable radix sort"): no torch kernel, no
+    allocation beyond ``out`` and ``workspace`` (uint8, at least ``pob_sort_workspace_bytes(n)``; see
+    ``sort_workspace``) where they are not passed in, no synchronisation.  On a CPU tensor it is
+    ``torch.sort(stable=True)`` on the words mapped to the signed order."""
+    if words.dtype != torch.uint32 or words.dim() != 1 or words.numel() < 1:
+        raise TypeError("words must be a non-empty torch.uint32 tensor of shape (n,)")
+    n = int(words.numel())
+    if words.device.type != "cuda":
+        if out is not None or workspace is not None:
+            raise ValueError("out and workspace belong to the device path")
+        return torch.sort(words.view(torch.int32) ^ (-2 ** 31), stable=True)[1].to(torch.int32)
+    words = words.contiguous()
+    out, workspace = _sort_buffers(n, words.device, out, workspace)
+    # vals = NULL: the payload is iota; keys_out = NULL: the sorted words are not wanted
+    check(lib.pob_sort_pairs_u32(words.data_ptr(), None, n, None, out.data_ptr(), workspace.data_ptr(),
+                                 workspace.numel(), _lib.stream_handle(words.device)))
+    return out
+
+
+def random_permutation(key: torch.Tensor, n: int, sort: str = "torch", workspace=None, out=None) -> torch.Tensor:
     """jax.random.permutation(key, n) -> int32 (n,), on the key's device ([ext], recalled: jax's
     ``_shuffle``, the scheme of the reset kernels' ``choice`` continued over every round).  x starts
     as arange(n); each of ``permutation_rounds(n)`` rounds takes ``key, sub = split(key)`` and sorts x
-    STABLY by ``random_bits(sub, (n,))``.  A device key takes the device threefry and
-    ``torch.sort(stable=True)`` on the words mapped to the signed order (no host work, no
-    synchronisation: capturable); a CPU key the host threefry and a stable argsort.  ``key`` itself
-    is only read."""
+    STABLY by ``random_bits(sub, (n,))``.  A CPU key takes the host threefry and a stable argsort,
+    whatever ``sort`` says.  A device key with ``sort="torch"`` (the default) takes the device threefry
+    and ``torch.sort(stable=True)`` on the words mapped to the signed order, one sort and one gather a
+    round; with ``sort="native"`` the whole of it is ONE ``pob_random_permutation`` call: the splits on
+    the device, the words formed inside the first pass of each round's radix sort, the engine's own
+    kernels throughout (DESIGN.md "Native stable radix sort"), into ``out`` (int32 (n,), allocated
+    where None) with ``workspace`` (uint8, ``sort_workspace(n, device)``, allocated where None) as its
+    only scratch memory.  Both device paths do no host work and no synchronisation, and give the bits
+    of the CPU path.  ``key`` itself is only read."""
+    if sort not in ("torch", "native"):
+        raise ValueError(f"sort must be 'torch' or 'native', got {sort!r}")
     key = torch.as_tensor(key)
     if key.dtype != torch.uint32 or key.numel() != 2:
         raise TypeError("key must be a torch.uint32 tensor of 2 words (random_prngkey)")
@@ -127,6 +182,11 @@ def random_permutation(key: torch.Tensor, n: int) -> torch.Tensor:
             x = x[torch.sort(_host_bits(sub, n), stable=True)[1]]
         return x
     key = key.contiguous()
+    if sort == "native":
+        out, workspace = _sort_buffers(n, key.device, out, workspace)
+        check(lib.pob_random_permutation(key.data_ptr(), n, out.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                         _lib.stream_handle(key.device)))
+        return out
     x = torch.arange(n, dtype=torch.int32, device=key.device)
     for _ in range(rounds):
         key, sub = random_split(key)

@@ -366,8 +366,8 @@ class _DeviceLearner:
         self.num_minibatches, self.num_update_epochs = int(num_minibatches), int(num_update_epochs)
         if optimizer not in ("torch", "fused"):
             raise ValueError(f"optimizer must be 'torch' or 'fused', got {optimizer!r}")
-        if permutation not in ("torch", "threefry"):
-            raise ValueError(f"permutation must be 'torch' or 'threefry', got {permutation!r}")
+        if permutation not in ("torch", "threefry", "native"):
+            raise ValueError(f"permutation must be 'torch', 'threefry' or 'native', got {permutation!r}")
         dev = self.policy.theta.device
         self.key = _networks._key_words(key).to(dev).clone()
         words = _networks._key_words(key).cpu()
@@ -382,7 +382,8 @@ class _DeviceLearner:
             self.optimizer = torch.optim.Adam(self._theta, lr=float(learning_rate))
         self.permutation = permutation
         self.perm_key = None
-        if permutation == "threefry":  # random_split(key, 3)[2], on the key's device
+        self._perm_workspace = None  # "native": the sort's scratch memory, allocated at the first draw and kept
+        if permutation != "torch":  # random_split(key, 3)[2], on the key's device
             if dev.type == "cuda":
                 from .. import jumpy
                 self.perm_key = jumpy.random_split_rows(self.key, 3, 2, 1).reshape(2)
@@ -407,9 +408,15 @@ class _DeviceLearner:
 
     def _draw_permutation(self, n: int, dev) -> torch.Tensor:
         """One epoch's int32 permutation of n items on ``dev``."""
-        if self.permutation == "threefry":
+        if self.permutation != "torch":
             from .. import jumpy
-            perm = jumpy.random_permutation(self.perm_key, n).to(dev)
+            if self.permutation == "native" and self.perm_key.is_cuda:
+                ws = self._perm_workspace
+                if ws is None or ws.numel() < jumpy.sort_workspace_bytes(n):
+                    ws = self._perm_workspace = jumpy.sort_workspace(n, self.perm_key.device)
+                perm = jumpy.random_permutation(self.perm_key, n, sort="native", workspace=ws).to(dev)
+            else:
+                perm = jumpy.random_permutation(self.perm_key, n).to(dev)
             _advance_key(self.perm_key)
             return perm
         return torch.randperm(n, device=dev, generator=self._generator).to(torch.int32)
@@ -459,7 +466,10 @@ class PPOLearner(_DeviceLearner):
     default: ``randperm`` from a generator seeded with ``key``) or ``"threefry"``: ``perm_key =
     random_split(key, 3)[2]`` lives on the device, each epoch draws ``jumpy.random_permutation(perm_key, T B)``
     (jax's shuffle, [ext]) and then ``perm_key <- split(perm_key)[0]``; ``key`` and the entropy draws are the
-    same either way.  With both nothing of an update is decided on the host (DESIGN.md "Learner on the
+    same either way.  ``"native"`` is ``"threefry"``'s key handling and bits with every draw one
+    ``pob_random_permutation`` call (``random_permutation(..., sort="native")``: the engine's radix sort in
+    place of ``torch.sort``, DESIGN.md "Native stable radix sort") through a workspace the learner
+    allocates once.  With both nothing of an update is decided on the host (DESIGN.md "Learner on the
     device").
 
     Not brax's: advantages and value targets are the replay's (not recomputed per minibatch), and
@@ -551,7 +561,7 @@ class RecurrentPPOLearner(_DeviceLearner):
     faster natively, and the vendor-GEMM argument holds for 256-wide dense layers only.  There is no
     gradient to ``value_hidden0``.
 
-    ``optimizer`` and ``permutation`` are ``PPOLearner``'s; the threefry permutation is over the B envs.
+    ``optimizer`` and ``permutation`` are ``PPOLearner``'s; the threefry and native permutations are over the B envs.
 
     Not brax's: advantages and value targets are the replay's, minibatches never cut a window shorter
     than T, and by default the permutation is torch's."""
