@@ -306,6 +306,26 @@ int pob_gru_policy_act_norm(const pob_gru *g, int B, int total, int first, const
 int pob_mlp_forward_wide(const pob_mlp *mlp, int B, const float *x, const float *theta, float *y, void *stream);
 int pob_mlp_forward_wide_norm(const pob_mlp *mlp, int B, const float *x, const float *theta, float *y,
                               const float *norm, float norm_clip, void *stream);
+/* The forward with bf16 operands on the matrix cores and f32 accumulation (ABI v8, additive;
+ * DESIGN.md "Bf16 forward"): an opt-in mixed-precision inference pass for wide networks over many
+ * rows.  x^ = bf16(x) (in the _norm form after the normaliser's f32 arithmetic, exactly
+ * pob_mlp_forward_norm's), W^ = bf16(W), per layer a = b + h^ W^ with exact products, f32
+ * accumulation from the f32 bias, h = act(a) in f32, h^ = bf16(h) for every hidden layer; the last
+ * layer's output is f32, unrounded.  bf16() rounds to nearest even.  The summation order is the
+ * matrix instruction's: the result is deterministic (the same bits from run to run) but NOT the
+ * fmaf chain of the f32 kernels; it is held to a float64 statement of the definition above within
+ * a tolerance.  theta (f32, never modified) and norm are read at launch time: every call first
+ * packs theta's matrices as bf16 into `workspace` (caller-owned device memory, 16-byte aligned, of
+ * pob_mlp_bf16_workspace_bytes = sum over the layers of roundup(in, 16) roundup(out, 32) 2 bytes,
+ * contents irrelevant between calls) on the same stream.  Every network pob_mlp_create accepts,
+ * every B >= 1; the error contract of pob_mlp_forward_wide, a NULL workspace rejected as the other
+ * pointers are.  No allocation, no synchronisation, no atomics: capturable.
+ * pob_mlp_bf16_workspace_bytes makes no HIP call. */
+int pob_mlp_bf16_workspace_bytes(const pob_mlp *mlp, long long *bytes);
+int pob_mlp_forward_bf16(const pob_mlp *mlp, int B, const float *x, const float *theta, float *y, void *workspace,
+                         void *stream);
+int pob_mlp_forward_bf16_norm(const pob_mlp *mlp, int B, const float *x, const float *theta, float *y,
+                              const float *norm, float norm_clip, void *workspace, void *stream);
 
 /* ---- generalised advantage estimation (ABI v8, additive): brax v1 PPO's compute_gae [ext] in one
  * launch, gae_ref of csrc/pob_mlp.h bit for bit (DESIGN.md "Critic pass and GAE": formula and

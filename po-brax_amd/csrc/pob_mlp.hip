@@ -6,6 +6,7 @@
 //   k_policy_act   the same forward, then the tanh-normal head (brax NormalTanhDistribution [ext])
 //
 // The tile code and its layout are pob_mlp_tile.h's.  The other network kernels:
+//   pob_mlp_bf16.hip   k_mlp_pack_bf16, k_mlp_forward_bf16: the opt-in bf16 matrix-core forward
 //   pob_gru.hip        k_gru_forward, k_gru_policy_act: the recurrent actor
 //   pob_mlp_train.hip  k_mlp_forward_train, k_mlp_bwd_* and their four-wave forms: the training passes
 //   pob_gru_seq.hip    k_gru_seq_forward, k_gru_seq_backward, k_gru_bwd_weights, k_gru_seq_infer: the recurrent window

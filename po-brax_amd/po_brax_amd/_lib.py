@@ -80,6 +80,7 @@ EXPORTS = (
     "pob_mlp_forward_wide", "pob_mlp_forward_wide_norm",
     "pob_mlp_forward_train_wide", "pob_mlp_backward_wide",
     "pob_sort_workspace_bytes", "pob_sort_pairs_u32", "pob_random_permutation",
+    "pob_mlp_bf16_workspace_bytes", "pob_mlp_forward_bf16", "pob_mlp_forward_bf16_norm",
 )
 MLP_WIDE_ROWS = 64  # MLPW_ROWS: the rows a block of k_mlp_forward_wide owns
 SORT_TILE = 2048  # POB_SORT_TILE: the elements a block of the radix sort owns
@@ -144,6 +145,10 @@ def _load():
     for name in ("pob_mlp_forward", "pob_mlp_forward_wide", "pob_policy_act", "pob_gru_forward", "pob_gru_policy_act"):
         plain = getattr(lib, name).argtypes
         getattr(lib, name + "_norm").argtypes = list(plain[:-1]) + [_VP, C.c_float, _VP]
+    # the bf16 forward: the plain lists with the workspace before the stream
+    lib.pob_mlp_bf16_workspace_bytes.argtypes = [_VP, C.POINTER(C.c_longlong)]
+    lib.pob_mlp_forward_bf16.argtypes = [_VP, C.c_int, _VP, _VP, _VP, _VP, _VP]
+    lib.pob_mlp_forward_bf16_norm.argtypes = [_VP, C.c_int, _VP, _VP, _VP, _VP, C.c_float, _VP, _VP]
     # T, B, truncation, second, done_input, reward, reward_scale, values, bootstrap, lambda, discount, vs, adv, stream
     lib.pob_gae.argtypes = [C.c_int, C.c_longlong, _VP, _VP, C.c_int, _VP, C.c_float, _VP, _VP, C.c_float, C.c_float,
                             _VP, _VP, _VP]

@@ -23,7 +23,7 @@ import torch
 from .. import _lib
 from .._lib import check, lib, ptr
 from . import normalization as _normalization
-from .networks import FeedForwardModel, Params, RecurrentModel, RecurrentParams, forward_entry
+from .networks import FeedForwardModel, Params, RecurrentModel, RecurrentParams, bf16_workspace, forward_entry
 
 
 def _gae_torch(truncation, termination, rewards, values, bootstrap_value, lambda_, discount, reward_scaling, vs, adv):
@@ -114,6 +114,9 @@ class ValueFunction:
     launch over (N, D) rows into an (N,) buffer: no allocation, no host sync, capture-safe.
     ``kernel="resident"`` makes it ``pob_mlp_forward_wide_norm`` (``networks.forward_entry``: the
     same values, the kernel laid out for a wide network over a whole trajectory's rows).
+    ``kernel="bf16"`` makes it ``pob_mlp_forward_bf16_norm``: the mixed-precision critic (bf16 operands
+    on the matrix cores, f32 accumulation: other values, DESIGN.md "Bf16 forward"), its workspace owned
+    by this object; the values feed GAE only, the learner recomputes them in f32.
     ``params.theta`` is read in place at launch time, so an optimiser step between replays is seen
     by a captured graph; so is the table of ``normalizer`` (a
     ``normalization.ObservationNormalizer`` of width ``obs_size``; the policy's, usually)."""
@@ -132,6 +135,9 @@ class ValueFunction:
         if theta.numel() != model.mlp.param_count:
             raise ValueError(f"theta has {theta.numel()} elements, the network {model.mlp.param_count}")
         self.model, self.params, self.theta = model, params, theta
+        # the bf16 forward's packed weights: allocated once, here, so that values_into never allocates
+        self.workspace = bf16_workspace(model.mlp, theta.device) if kernel == "bf16" else None
+        self._extra = () if self.workspace is None else (ptr(self.workspace),)
 
     def values_into(self, obs_rows: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
         """``out`` (N,) <- the value of every row of ``obs_rows`` (N, D); both contiguous float32
@@ -148,7 +154,7 @@ class ValueFunction:
         norm = self.normalizer
         check(self._forward(self.model.mlp.handle, N, ptr(obs_rows), ptr(self.theta), ptr(out),
                             None if norm is None else ptr(norm.table), 0.0 if norm is None else norm.clip,
-                            _lib.stream_handle(dev)))
+                            *self._extra, _lib.stream_handle(dev)))
         return out
 
     def __call__(self, obs: torch.Tensor) -> torch.Tensor:

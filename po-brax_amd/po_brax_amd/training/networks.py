@@ -171,7 +171,39 @@ def _forward_torch(sizes, act: int, theta_or_params, x: torch.Tensor) -> torch.T
     return h
 
 
-FORWARD_KERNELS = {"tile": "pob_mlp_forward", "resident": "pob_mlp_forward_wide"}
+def _bf16(t: torch.Tensor) -> torch.Tensor:
+    return t.to(torch.bfloat16).to(t.dtype)  # round to nearest even, the value kept in t's own type
+
+
+def _forward_torch_bf16(sizes, act: int, theta_or_params, x: torch.Tensor) -> torch.Tensor:
+    """The definition of ``kernel="bf16"`` (DESIGN.md "Bf16 forward") in torch ops: input, weights and
+    every hidden activation rounded to bf16, biases, sums and activations in the tensors' own type."""
+    theta = getattr(theta_or_params, "theta", None)
+    h, off = _bf16(x), 0
+    n = len(sizes) - 1
+    for i, (n_in, n_out) in enumerate(zip(sizes[:-1], sizes[1:])):
+        if theta is not None:
+            W = theta[off:off + n_in * n_out].view(n_in, n_out)
+            off += n_in * n_out
+            b = theta[off:off + n_out]
+            off += n_out
+        else:
+            W, b = theta_or_params[f"hidden_{i}"]["kernel"], theta_or_params[f"hidden_{i}"]["bias"]
+        h = torch.addmm(b, h.reshape(-1, n_in), _bf16(W)).reshape(*h.shape[:-1], n_out)
+        if i != n - 1:
+            h = _bf16(_TORCH_ACT[act](h))
+    return h
+
+
+def bf16_workspace(mlp: "MLPHandle", device) -> torch.Tensor:
+    """The workspace of the bf16 forward for this network (``pob_mlp_bf16_workspace_bytes``): the
+    packed weights, rewritten by every call."""
+    need = C.c_longlong()
+    check(lib.pob_mlp_bf16_workspace_bytes(mlp.handle, C.byref(need)))
+    return torch.empty(need.value // 2, dtype=torch.bfloat16, device=device)
+
+
+FORWARD_KERNELS = {"tile": "pob_mlp_forward", "resident": "pob_mlp_forward_wide", "bf16": "pob_mlp_forward_bf16"}
 # the training pass under the same names: (forward with the pre-activations kept, backward)
 TRAIN_KERNELS = {"tile": ("pob_mlp_forward_train", "pob_mlp_backward"),
                  "resident": ("pob_mlp_forward_train_wide", "pob_mlp_backward_wide")}
@@ -180,7 +212,9 @@ TRAIN_KERNELS = {"tile": ("pob_mlp_forward_train", "pob_mlp_backward"),
 def forward_entry(kernel: str, norm: bool = False):
     """The fused forward's entry point: ``"tile"`` (one wave per 32 rows: the actor's widths) or
     ``"resident"`` (four waves per 64 rows, a weight fragment used for both row sub-tiles: wide
-    layers over many rows; DESIGN.md "Wide forward").  The two give the same bits."""
+    layers over many rows; DESIGN.md "Wide forward").  The two give the same bits.  ``"bf16"`` is another
+    function (bf16 operands on the matrix cores, f32 accumulation: DESIGN.md "Bf16 forward") and takes a
+    workspace (``bf16_workspace``) before the stream."""
     if kernel not in FORWARD_KERNELS:
         raise ValueError(f"kernel must be one of {sorted(FORWARD_KERNELS)}, got {kernel!r}")
     return getattr(lib, FORWARD_KERNELS[kernel] + ("_norm" if norm else ""))
@@ -233,7 +267,7 @@ def make_model(layer_sizes: Sequence[int], obs_size: int, activation: Any = "swi
         fused = (theta is not None and x.is_cuda and x.dtype == torch.float32 and theta.is_cuda
                  and theta.dtype == torch.float32 and theta.is_contiguous() and not need_grad)
         if not fused:
-            return _forward_torch(sizes, act, params, x)
+            return (_forward_torch_bf16 if kernel == "bf16" else _forward_torch)(sizes, act, params, x)
         if theta.numel() != mlp.param_count:
             raise ValueError(f"theta has {theta.numel()} elements, the network {mlp.param_count}")
         if x.shape[-1] != sizes[0]:
@@ -241,7 +275,9 @@ def make_model(layer_sizes: Sequence[int], obs_size: int, activation: Any = "swi
         x2 = x.detach().reshape(-1, sizes[0]).contiguous()
         y = torch.empty((x2.shape[0], sizes[-1]), dtype=torch.float32, device=x.device)
         if x2.shape[0]:
-            check(forward(mlp.handle, x2.shape[0], ptr(x2), ptr(theta.detach()), ptr(y), _lib.stream_handle(x.device)))
+            extra = (ptr(bf16_workspace(mlp, x.device)),) if kernel == "bf16" else ()
+            check(forward(mlp.handle, x2.shape[0], ptr(x2), ptr(theta.detach()), ptr(y), *extra,
+                          _lib.stream_handle(x.device)))
         return y.reshape(*x.shape[:-1], sizes[-1])
 
     class _NativeMLP(torch.autograd.Function):

@@ -1,10 +1,11 @@
-"""mlp_wide_bench.py -- the critic's value launch through both fused forwards.
+"""mlp_wide_bench.py -- the critic's value launch through the three fused forwards.
 
 (a) ValueFunction.values_into alone, HH's value network [114 -> 256 x 5 -> 1] under a normaliser,
-    kernel="tile" (pob_mlp_forward_norm: the baseline) against kernel="resident"
-    (pob_mlp_forward_wide_norm), at 2^10 .. 2^20 rows in powers of four and at the critic pass's
-    (T + 1) B = 1 376 256; the two alternate call by call in one process and the outputs are
-    compared bit for bit.
+    kernel="tile" (pob_mlp_forward_norm) against kernel="resident" (pob_mlp_forward_wide_norm) and
+    kernel="bf16" (pob_mlp_forward_bf16_norm, its pack pass included), at 2^10 .. 2^20 rows in
+    powers of four and at the critic pass's (T + 1) B = 1 376 256; the three alternate call by call
+    in one process; "tile" and "resident" are compared bit for bit, "bf16" (another function) by
+    its largest |difference| from "resident".
 (b) AntHeavenHell, B = 65 536, T = 20: one ActorRollout replay with each critic, in turn.
 
 Prints one JSON line.
@@ -25,7 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from gae_bench import interleaved  # noqa: E402
 
-KERNELS = ("tile", "resident")
+KERNELS = ("tile", "resident", "bf16")
 
 
 def summary(ms):
@@ -57,7 +58,9 @@ def bench_alone(row_counts, rounds, warmup, D=114):
         for k in KERNELS:
             s[k]["TFLOPs"] = round(N * flop_per_row / (s[k]["median_ms"] * 1e-3) / 1e12, 2)
         out.append({"rows": N, **s, "tile_over_resident": round(s["tile"]["median_ms"] / s["resident"]["median_ms"], 3),
-                    "bit_equal": bool(torch.equal(y["tile"], y["resident"]))})
+                    "resident_over_bf16": round(s["resident"]["median_ms"] / s["bf16"]["median_ms"], 3),
+                    "bit_equal": bool(torch.equal(y["tile"], y["resident"])),
+                    "bf16_max_abs_diff": float((y["bf16"] - y["resident"]).abs().max())})
     return out
 
 
@@ -77,7 +80,9 @@ def bench_rollout(B, T, rounds, warmup):
         rolls[k] = ActorRollout(env, env.reset(keys), pol, T, update_normalizer=True, critic=critics(D, norm)[1][k])
     ms = interleaved({k: r.replay for k, r in rolls.items()}, rounds, warmup)
     same = all(bool(torch.equal(getattr(rolls["tile"], a), getattr(rolls["resident"], a))) for a in ("values", "vs", "advantages"))
-    return {"env": "ant_heavenhell", "batch": B, "steps": T, "replay": summary(ms), "bit_equal": same}
+    diff = {a: float((getattr(rolls["bf16"], a) - getattr(rolls["resident"], a)).abs().max()) for a in ("values", "advantages")}
+    return {"env": "ant_heavenhell", "batch": B, "steps": T, "replay": summary(ms), "bit_equal": same,
+            "bf16_max_abs_diff": diff}
 
 
 def main():
