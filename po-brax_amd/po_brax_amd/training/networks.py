@@ -195,6 +195,63 @@ def _forward_torch_bf16(sizes, act: int, theta_or_params, x: torch.Tensor) -> to
     return h
 
 
+def _activate_grad(act: int, z: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """``mlp_activate_grad`` of csrc/pob_mlp.h in torch ops (relu gives 0 wherever z <= 0)."""
+    if act == 0:
+        return torch.where(z > 0, g, torch.zeros_like(g))
+    if act == 1:
+        s = torch.sigmoid(z)
+        return g * (s + z * s * (1 - s))
+    t = torch.tanh(z)
+    return g * (1 - t * t)
+
+
+class _MixedTorch(torch.autograd.Function):
+    """The definition of ``kernel="mixed"`` (DESIGN.md "Mixed training pass") in torch ops: ``_forward_torch_bf16``
+    forward; backward written out, the rounding points as identities and every product's operands rounded
+    (autograd through ``.to(torch.bfloat16)`` would round the gradients themselves: another function).
+    Arguments: act, act_final, x (M, in), then W_0, b_0, W_1, b_1, ..."""
+
+    @staticmethod
+    def forward(ctx, act, act_final, x, *wb):
+        n = len(wb) // 2
+        h, keep = _bf16(x), []
+        for i in range(n):
+            keep.append(h)
+            z = torch.addmm(wb[2 * i + 1], h, _bf16(wb[2 * i]))
+            keep.append(z)
+            h = _bf16(_TORCH_ACT[act](z)) if i != n - 1 else (_TORCH_ACT[act](z) if act_final else z)
+        ctx.act, ctx.act_final = act, act_final
+        ctx.save_for_backward(*keep, *wb[::2])
+        return h
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        n = len(ctx.saved_tensors) // 3
+        keep, Ws = ctx.saved_tensors[:2 * n], ctx.saved_tensors[2 * n:]
+        grads, g = [None] * (2 * n), dy
+        for i in reversed(range(n)):
+            h, z = keep[2 * i], keep[2 * i + 1]
+            d = _bf16(_activate_grad(ctx.act, z, g) if i != n - 1 or ctx.act_final else g)
+            grads[2 * i], grads[2 * i + 1] = h.t() @ d, d.sum(0)
+            if i or ctx.needs_input_grad[2]:
+                g = d @ _bf16(Ws[i]).t()
+        return (None, None, g if ctx.needs_input_grad[2] else None, *grads)
+
+
+def _mixed_torch(sizes, act: int, theta_or_params, x: torch.Tensor, act_final: bool = False) -> torch.Tensor:
+    theta = getattr(theta_or_params, "theta", None)
+    wb, off = [], 0
+    for i, (n_in, n_out) in enumerate(zip(sizes[:-1], sizes[1:])):
+        if theta is not None:
+            wb += [theta[off:off + n_in * n_out].view(n_in, n_out), theta[off + n_in * n_out:off + (n_in + 1) * n_out]]
+            off += (n_in + 1) * n_out
+        else:
+            wb += [theta_or_params[f"hidden_{i}"]["kernel"], theta_or_params[f"hidden_{i}"]["bias"]]
+    return _MixedTorch.apply(act, act_final, x.reshape(-1, sizes[0]), *wb).reshape(*x.shape[:-1], sizes[-1])
+
+
 def bf16_workspace(mlp: "MLPHandle", device) -> torch.Tensor:
     """The workspace of the bf16 forward for this network (``pob_mlp_bf16_workspace_bytes``): the
     packed weights, rewritten by every call."""
@@ -319,17 +376,25 @@ def make_model(layer_sizes: Sequence[int], obs_size: int, activation: Any = "swi
         it); ``kernel="resident"`` makes them ``pob_mlp_forward_train_wide`` and ``pob_mlp_backward_wide``
         (``train_entries``: the same bits, laid out for a wide network over many rows).  Anything else
         (the CPU, other dtypes, the dict-of-views form) takes the torch ops under autograd, where
-        ``kernel`` selects nothing; when no gradient is needed this is ``apply``."""
-        entries = train_entries(kernel)
+        ``kernel`` selects nothing; when no gradient is needed this is ``apply``.
+
+        ``kernel="mixed"`` is another function, the mixed-precision training pass (DESIGN.md "Mixed training
+        pass": f32 master weights, bf16 operands, f32 sums): the values of ``apply(kernel="bf16")``, which it is
+        without grad, and under grad the definition in torch ops.  It has no kernels yet: where the engine's
+        backward would run (contiguous float32 CUDA ``theta`` and ``x``) it raises ``NotImplementedError``."""
+        mixed = kernel == "mixed"
+        entries = None if mixed else train_entries(kernel)
         theta = getattr(params, "theta", None)
         need_grad = torch.is_grad_enabled() and (x.requires_grad or (
             theta.requires_grad if theta is not None else any(t.requires_grad for p in params.values() for t in p.values())))
         if not need_grad:
-            return apply(params, x, kernel)
+            return apply(params, x, "bf16" if mixed else kernel)
         native = (theta is not None and x.is_cuda and x.dtype == torch.float32 and theta.is_cuda
                   and theta.dtype == torch.float32 and theta.is_contiguous() and x.numel() > 0)
         if not native:
-            return _forward_torch(sizes, act, params, x)
+            return (_mixed_torch if mixed else _forward_torch)(sizes, act, params, x)
+        if mixed:
+            raise NotImplementedError("kernel=\"mixed\" has no native training pass (DESIGN.md \"Mixed training pass\")")
         if theta.numel() != mlp.param_count:
             raise ValueError(f"theta has {theta.numel()} elements, the network {mlp.param_count}")
         if x.shape[-1] != sizes[0]:
