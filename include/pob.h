@@ -263,6 +263,18 @@ int pob_gru_policy_act(const pob_gru *g, int B, int total, int first, const floa
                        uint32_t *key_io, int deterministic, const float *reset, float *h_io, float *action,
                        float *logp, float *raw, float *logits, float *obs_copy, float *h_in_copy, void *stream);
 
+/* ---- recurrent actor, LSTM cell (additive to ABI v8): the network above with the cell swapped;
+ * results follow lstm_forward_ref of csrc/pob_mlp.h (DESIGN.md "LSTM cell").  pob_lstm_create takes
+ * pob_gru_create's arguments and limits and returns a pob_gru whose cell is an LSTM, gates in
+ * torch.nn.LSTMCell's order (i, f, g, o), with cat = [x ; h]:
+ *   a = b + cat W,  c' = sigmoid(a_f) c + sigmoid(a_i) tanh(a_g),  h' = sigmoid(a_o) tanh(c').
+ * `theta`: the pre-MLP's W, b pairs, W (I + H, 4 H), b (4 H), the post-MLP's pairs.  The state is
+ * ONE row [h ; c]: for such a handle h_io and h_in_copy are (B, 2 H) and reset zeroes all 2 H
+ * columns.  pob_gru_destroy, pob_gru_param_count, pob_gru_forward(_norm) and pob_gru_policy_act(_norm)
+ * serve it; the pob_gru_sequence_* entry points return POB_EINVAL for it before any HIP call. */
+int pob_lstm_create(int n_pre, const int *pre_sizes, int hidden, int n_post, const int *post_sizes, int activation,
+                    pob_gru **out);
+
 /* ---- running observation normaliser (additive to ABI v8): brax PPO's normalize_observations
  * (brax <= 0.0.12 training/normalization.py [ext]); results equal obsnorm_accumulate_ref /
  * obsnorm_update_ref / pob_obsnorm_apply of csrc/pob_mlp.h bit for bit (DESIGN.md "Observation

@@ -7,7 +7,7 @@
 // The cell and the pool's layout are pob_gru_tile.h's.
 #include <new>
 
-#include "pob_gru_tile.h"
+#include "pob_lstm_tile.h"
 #include "pob_policy_head.h"
 
 // The forward of one tile; h' is stored to h_io on the way.  Returns the image holding the post-
@@ -86,10 +86,11 @@ __global__ __launch_bounds__(64) void k_gru_policy_act(const GruDesc d, const in
   policy_tile_head(L, T, A, b0, valid, total, first, key, deterministic, action, logp, raw, logits, lane);
 }
 
-extern "C" {
-
-int pob_gru_create(int n_pre, const int *pre_sizes, int hidden, int n_post, const int *post_sizes, int activation,
-                   pob_gru **out) {
+// pob_gru_create and pob_lstm_create: the limits and the descriptor are the same, the cell's share
+// of theta and the pool's plan are not.  The messages keep the "gru:" prefix for either cell: they
+// name limits of the recurrent network, not of the cell.
+static int recurrent_create(const int cell, int n_pre, const int *pre_sizes, int hidden, int n_post, const int *post_sizes,
+                            int activation, pob_gru **out) {
   if (!out) return pob_fail_msg(POB_EINVAL, "gru: out is NULL");
   *out = nullptr;
   if (!pre_sizes || !post_sizes) return pob_fail_msg(POB_EINVAL, "gru: sizes is NULL");
@@ -115,14 +116,27 @@ int pob_gru_create(int n_pre, const int *pre_sizes, int hidden, int n_post, cons
   long long n = 0;
   for (int l = 0; l < n_pre; ++l) n += ((long long)d.pre[l] + 1) * d.pre[l + 1];
   const long long I = d.pre[n_pre], H = hidden;
-  n += 3 * H * I + 3 * H * H + 4 * H;
+  n += cell == POB_CELL_LSTM ? 4 * H * (I + H) + 4 * H : 3 * H * I + 3 * H * H + 4 * H;
   long long in = H;
   for (int l = 0; l < n_post; ++l) { n += (in + 1) * d.post[l]; in = d.post[l]; }
   g->n_params = n;
-  g->cls_forward = gru_plan(d, false, nullptr);
-  g->cls_actor = gru_plan(d, true, nullptr);
+  g->cell = cell;
+  g->cls_forward = cell == POB_CELL_LSTM ? lstm_plan(d, false, nullptr) : gru_plan(d, false, nullptr);
+  g->cls_actor = cell == POB_CELL_LSTM ? lstm_plan(d, true, nullptr) : gru_plan(d, true, nullptr);
   *out = g;
   return POB_OK;
+}
+
+extern "C" {
+
+int pob_gru_create(int n_pre, const int *pre_sizes, int hidden, int n_post, const int *post_sizes, int activation,
+                   pob_gru **out) {
+  return recurrent_create(POB_CELL_GRU, n_pre, pre_sizes, hidden, n_post, post_sizes, activation, out);
+}
+
+int pob_lstm_create(int n_pre, const int *pre_sizes, int hidden, int n_post, const int *post_sizes, int activation,
+                    pob_gru **out) {
+  return recurrent_create(POB_CELL_LSTM, n_pre, pre_sizes, hidden, n_post, post_sizes, activation, out);
 }
 
 void pob_gru_destroy(pob_gru *g) { delete g; }
@@ -139,10 +153,11 @@ int pob_gru_forward_norm(const pob_gru *g, int B, const float *x, const float *t
   if (B < 1) return pob_fail_msg(POB_EINVAL, "gru: batch size must be positive");
   if (!x || !theta || !y) return pob_fail_msg(POB_EINVAL, "gru: NULL argument");
   if (!h_io) return pob_fail_msg(POB_EINVAL, "gru: h_io is NULL");
+  hipStream_t st = (hipStream_t)stream;
+  if (g->cell == POB_CELL_LSTM) return lstm_forward_launch(g, B, x, theta, reset, h_io, y, h_in_copy, norm, norm_clip, st);
   GruDesc d = g->d;
   gru_plan(d, false, d.p_rows);
   const dim3 grid = mlp_tile_grid(B);
-  hipStream_t st = (hipStream_t)stream;
   TILE_DISPATCH(k_gru_forward, g->cls_forward, GRU_HEIGHTS, d, B, x, theta, reset, h_io, y, h_in_copy)
   return mlp_hip_check(hipGetLastError(), "k_gru_forward launch");
 }
@@ -165,10 +180,13 @@ int pob_gru_policy_act_norm(const pob_gru *g, int B, int total, int first, const
   if (!obs || !theta || !action) return pob_fail_msg(POB_EINVAL, "policy: NULL argument");
   if (!h_io) return pob_fail_msg(POB_EINVAL, "policy: h_io is NULL");
   if (!deterministic && !key_io) return pob_fail_msg(POB_EINVAL, "policy: key is NULL");
+  hipStream_t st = (hipStream_t)stream;
+  if (g->cell == POB_CELL_LSTM)
+    return lstm_policy_act_launch(g, B, total, first, obs, theta, key_io, deterministic, reset, h_io, action, logp, raw,
+                                  logits, obs_copy, h_in_copy, norm, norm_clip, st);
   GruDesc d = g->d;
   gru_plan(d, true, d.p_rows);
   const dim3 grid = mlp_tile_grid(B);
-  hipStream_t st = (hipStream_t)stream;
   const uint32_t *key = key_io;
   TILE_DISPATCH(k_gru_policy_act, g->cls_actor, GRU_HEIGHTS, d, B, total, first, obs, theta, key, deterministic, reset, h_io,
                 action, logp, raw, logits, obs_copy, h_in_copy)

@@ -490,6 +490,8 @@ static int gru_seq_backward_rows(const GruDesc &d) { return 5 * d.hid + 2 * gru_
 // every limit of the sequence entry points, before any HIP call
 static int gru_seq_check(const pob_gru *g, int T, long long M, long long B, bool have_idx, GruSeqArgs *a) {
   if (!g) return pob_fail_msg(POB_EINVAL, "gru is NULL");
+  if (g->cell != POB_CELL_GRU)
+    return pob_fail_msg(POB_EINVAL, "gru sequence: the handle's cell is an lstm; the sequence kernels serve the gru cell only");
   if (T < 1) return pob_fail_msg(POB_EINVAL, "gru sequence: the step count T must be positive");
   if (M < 1) return pob_fail_msg(POB_EINVAL, "gru sequence: the sequence count M must be positive");
   if (B < 1) return pob_fail_msg(POB_EINVAL, "gru sequence: the env count B must be positive");

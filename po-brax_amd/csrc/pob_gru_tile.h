@@ -52,8 +52,11 @@ POB_MLP_D void gru_cell(const float *C, float *N, const float *g, const int I, c
 struct pob_gru {
   GruDesc d;
   long long n_params;
-  int cls_forward, cls_actor;  // pool height classes (GRU_HEIGHTS)
+  int cls_forward, cls_actor;  // pool height classes (GRU_HEIGHTS; an LSTM handle's: LSTM_HEIGHTS)
+  int cell;                    // POB_CELL_GRU, or POB_CELL_LSTM (pob_lstm_create: pob_lstm_tile.h)
 };
+#define POB_CELL_GRU 0
+#define POB_CELL_LSTM 1
 
 // The heights of P0 and P1, by the walk of gru_tile_forward; with `head` the actor's terms (A features) go to
 // the image the logits are not in.  Returns the pool's height class (0 .. 4:

@@ -750,6 +750,85 @@ static inline void gru_policy_ref(const int n_pre, const int *pre_sizes, const i
   gru_forward_ref(n_pre, pre_sizes, H, n_post, post_sizes, activation, B, obs, theta, reset, h_in, logits, h_out, h_in_copy);
   policy_head_ref(B, post_sizes[n_post - 1] >> 1, logits, u, deterministic, action, logp, raw);
 }
+
+// ---------------------------------------------------------------------------- recurrent actor, LSTM cell
+// The network above with the cell swapped (DESIGN.md "LSTM cell").  theta: the pre-MLP's pairs, W
+// (I + H, 4 H), b (4 H), the post-MLP's pairs.  With cat = [x ; h], gate q = 0 (i), 1 (f), 2 (g), 3 (o):
+//   a_q[j] = b[q H + j] + sum_k cat[k] W[k][q H + j]                    (the chain of mlp_chain_ref)
+//   c'[j]  = fmaf(sigmoid(a_1[j]), c[j], sigmoid(a_0[j]) tanh(a_2[j]))
+//   h'[j]  = sigmoid(a_3[j]) tanh(c'[j])
+// The state is ONE row [h ; c] of 2 H floats.
+static inline long long lstm_param_count(const int n_pre, const int *pre_sizes, const int H, const int n_post,
+                                         const int *post_sizes) {
+  long long n = 0;
+  for (int l = 0; l < n_pre; ++l) n += ((long long)pre_sizes[l] + 1) * pre_sizes[l + 1];
+  n += 4LL * H * (pre_sizes[n_pre] + H) + 4 * H;
+  int in = H;
+  for (int l = 0; l < n_post; ++l) { n += ((long long)in + 1) * post_sizes[l]; in = post_sizes[l]; }
+  return n;
+}
+// One env's cell: cat = [x ; h] (I + H contiguous floats), c (H), g = the LSTM block of theta.
+// Writes hn, cn (H each); cn may be c.
+static inline void lstm_cell_ref(const int I, const int H, const float *cat, const float *c, const float *g, float *hn,
+                                 float *cn) {
+  const float *W = g, *b = W + (long long)(I + H) * 4 * H;
+  for (int j = 0; j < H; ++j) {
+    const float ig = pob_sigmoidf(mlp_chain_ref(b[j], W, 4 * H, j, cat, I + H));
+    const float fg = pob_sigmoidf(mlp_chain_ref(b[H + j], W, 4 * H, H + j, cat, I + H));
+    const float gg = pob_tanhf(mlp_chain_ref(b[2 * H + j], W, 4 * H, 2 * H + j, cat, I + H));
+    const float og = pob_sigmoidf(mlp_chain_ref(b[3 * H + j], W, 4 * H, 3 * H + j, cat, I + H));
+    cn[j] = MLP_FMA(fg, c[j], ig * gg);
+    hn[j] = og * pob_tanhf(cn[j]);
+  }
+}
+// gru_forward_ref with the LSTM cell: s_in, s_out and s_in_copy are (B, 2 H) = [h ; c]; a reset row
+// starts from +0 in all 2 H columns.  s_out may be s_in.
+static inline void lstm_forward_ref(const int n_pre, const int *pre_sizes, const int H, const int n_post,
+                                    const int *post_sizes, const int activation, const int B, const float *x,
+                                    const float *theta, const float *reset, const float *s_in, float *y, float *s_out,
+                                    float *s_in_copy) {
+  float a[POB_MLP_MAX_WIDTH + 1], o[POB_MLP_MAX_WIDTH + 1], cat[POB_MLP_MAX_WIDTH + 1];
+  float c[POB_GRU_MAX_HIDDEN], hn[POB_GRU_MAX_HIDDEN];
+  const int D = pre_sizes[0], I = pre_sizes[n_pre], out_w = post_sizes[n_post - 1];
+  for (int b = 0; b < B; ++b) {
+    for (int k = 0; k < D; ++k) a[k] = x[(long long)b * D + k];
+    const float *W = theta;
+    for (int l = 0; l < n_pre; ++l) {
+      const int in = pre_sizes[l], out = pre_sizes[l + 1];
+      const float *bias = W + (long long)in * out;
+      for (int j = 0; j < out; ++j) o[j] = mlp_activate(activation, mlp_chain_ref(bias[j], W, out, j, a, in));
+      for (int j = 0; j < out; ++j) a[j] = o[j];
+      W = bias + out;
+    }
+    for (int k = 0; k < I; ++k) cat[k] = a[k];
+    const bool zero = reset && reset[b] != 0.0f;
+    for (int k = 0; k < 2 * H; ++k) {
+      const float s = zero ? 0.0f : s_in[(long long)b * 2 * H + k];
+      if (k < H) cat[I + k] = s; else c[k - H] = s;
+      if (s_in_copy) s_in_copy[(long long)b * 2 * H + k] = s;
+    }
+    lstm_cell_ref(I, H, cat, c, W, hn, c);
+    W += 4LL * H * (I + H) + 4 * H;
+    for (int k = 0; k < H; ++k) {
+      s_out[(long long)b * 2 * H + k] = hn[k];
+      s_out[(long long)b * 2 * H + H + k] = c[k];
+      a[k] = hn[k];
+    }
+    int in = H;
+    for (int l = 0; l < n_post; ++l) {
+      const int out = post_sizes[l];
+      const float *bias = W + (long long)in * out;
+      for (int j = 0; j < out; ++j) {
+        const float acc = mlp_chain_ref(bias[j], W, out, j, a, in);
+        o[j] = l != n_post - 1 ? mlp_activate(activation, acc) : acc;
+      }
+      for (int j = 0; j < out; ++j) a[j] = o[j];
+      W = bias + out;
+      in = out;
+    }
+    for (int j = 0; j < out_w; ++j) y[(long long)b * out_w + j] = a[j];
+  }
+}
 #endif
 
 // ---------------------------------------------------------------------------- recurrent backward

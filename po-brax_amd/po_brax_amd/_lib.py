@@ -69,6 +69,7 @@ EXPORTS = (
     "pob_env_set_obs_mask",
     "pob_mlp_create", "pob_mlp_destroy", "pob_mlp_param_count", "pob_mlp_forward", "pob_policy_act",
     "pob_gru_create", "pob_gru_destroy", "pob_gru_param_count", "pob_gru_forward", "pob_gru_policy_act",
+    "pob_lstm_create",
     "pob_obsnorm_workspace_bytes", "pob_obsnorm_accumulate", "pob_obsnorm_update",
     "pob_mlp_forward_norm", "pob_policy_act_norm", "pob_gru_forward_norm", "pob_gru_policy_act_norm",
     "pob_gae",
@@ -131,6 +132,7 @@ def _load():
                                    _VP, _VP]
     lib.pob_gru_create.argtypes = [C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int,
                                    C.POINTER(_VP)]
+    lib.pob_lstm_create.argtypes = lib.pob_gru_create.argtypes
     lib.pob_gru_destroy.argtypes = [_VP]
     lib.pob_gru_destroy.restype = None
     lib.pob_gru_param_count.argtypes = [_VP, C.POINTER(C.c_longlong)]

@@ -432,7 +432,8 @@ class RecurrentActorRollout:
     step ended an episode: at step t its ``reset`` input is ``done[t - 1]``, the trajectory
     row already on the device, and at t = 0 it is ``policy.reset``, into which the graph's last
     node copies ``done[T - 1]`` -- so state and episode boundaries carry across replays with
-    no host work.
+    no host work.  Under an LSTM policy (``make_recurrent_model(..., cell="lstm")``) the launch is
+    ``k_lstm_policy_act`` and every (B, H) below is (B, 2 H) = ``[h ; c]``, zeroed in all 2 H columns.
 
         roll = RecurrentActorRollout(env, state, policy, steps=T)
         roll.replay()
@@ -469,7 +470,7 @@ class RecurrentActorRollout:
         if not (obs.is_cuda and obs.dtype == torch.float32 and obs.dim() == 2):
             raise ValueError("the observation must be a float32 (B, D) device tensor")
         B, D = int(obs.shape[0]), int(obs.shape[1])
-        A, H = env.action_size, policy.hidden_size
+        A, H = env.action_size, policy.state_size  # the carried state's width: 2 H = [h ; c] under an LSTM policy
         if policy.action_size != A or policy.obs_size != D:
             raise ValueError(f"the policy maps {policy.obs_size} -> {policy.action_size}, the env {D} -> {A}")
         self.env, self.state, self.policy, self.steps = env, state, policy, int(steps)

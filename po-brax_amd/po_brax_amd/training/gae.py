@@ -175,6 +175,8 @@ class RecurrentValueFunction:
     def __init__(self, model: RecurrentModel, params: RecurrentParams, normalizer=None):
         if getattr(model, "gru", None) is None or getattr(model, "post_sizes", None) is None:
             raise ValueError("model must come from make_recurrent_model")
+        if getattr(model, "cell", "gru") != "gru":
+            raise ValueError(f"the recurrent critic runs the GRU window kernel: cell={model.cell!r} is not supported")
         if model.post_sizes[-1] != 1:
             raise ValueError(f"the value network's last width must be 1, got {model.post_sizes[-1]}")
         theta = params.theta

@@ -16,6 +16,8 @@ networks".
 ``make_recurrent_model`` / ``RecurrentTanhPolicy`` are the recurrent counterparts (pre-MLP ->
 GRU cell -> post-MLP, ``pob_gru_forward`` / ``pob_gru_policy_act``, the hidden state carried on
 the device), unrolled by ``rollout.RecurrentActorRollout``: DESIGN.md "Recurrent actor".
+``make_recurrent_model(..., cell="lstm")`` swaps the cell for an LSTM (``pob_lstm_create``, the kernels of
+``csrc/pob_lstm.hip``; the carried state is then (B, 2 H) = ``[h ; c]``): DESIGN.md "LSTM cell".
 ``model.apply_sequence`` runs a window of T steps in torch ops and ``model.apply_sequence_native`` in
 the engine, forward and truncated-BPTT backward (``pob_gru_sequence_forward_train`` /
 ``pob_gru_sequence_backward``): DESIGN.md "Recurrent backward".
@@ -419,17 +421,19 @@ MAX_HIDDEN, MAX_PRE, MAX_POST = 128, 3, 4
 class GRUHandle:
     """A ``pob_gru`` (shape and activation only: host memory, no HIP call to make or free)."""
 
-    def __init__(self, pre_sizes: Sequence[int], hidden: int, post_sizes: Sequence[int], activation: int):
+    def __init__(self, pre_sizes: Sequence[int], hidden: int, post_sizes: Sequence[int], activation: int,
+                 cell: str = "gru"):
         self.pre_sizes = [int(s) for s in pre_sizes]  # [obs width, *pre-MLP widths]
         self.post_sizes = [int(s) for s in post_sizes]
         self.hidden = int(hidden)
+        self.cell = cell  # "lstm": pob_lstm_create, the same handle type with the LSTM kernels behind it
         if not self.pre_sizes:
             raise ValueError("gru: pre_sizes must start with the observation width")
         pre = (C.c_int * len(self.pre_sizes))(*self.pre_sizes)
         post = (C.c_int * max(1, len(self.post_sizes)))(*self.post_sizes)
         h = C.c_void_p()
-        check(lib.pob_gru_create(len(self.pre_sizes) - 1, pre, self.hidden, len(self.post_sizes), post, int(activation),
-                                 C.byref(h)))
+        create = lib.pob_lstm_create if cell == "lstm" else lib.pob_gru_create
+        check(create(len(self.pre_sizes) - 1, pre, self.hidden, len(self.post_sizes), post, int(activation), C.byref(h)))
         self._h = h
         n = C.c_longlong()
         check(lib.pob_gru_param_count(h, C.byref(n)))
@@ -445,12 +449,16 @@ class GRUHandle:
             lib.pob_gru_destroy(h)
 
 
-def _gru_layout(pre_sizes, hidden, post_sizes):
+def _gru_layout(pre_sizes, hidden, post_sizes, cell="gru"):
     """``[(path, n_in, n_out)]`` of the weight matrices in ``theta`` order (each followed by its
-    bias of n_out entries); path = ("pre_i",), ("gru", "rz" | "xn" | "hn") or ("post_i",)."""
+    bias of n_out entries); path = ("pre_i",), ("gru", "rz" | "xn" | "hn") or ("post_i",); under
+    ``cell="lstm"`` the cell is the one matrix ("lstm",) of shape (I + H, 4 H)."""
     I, H = pre_sizes[-1], hidden
     out = [((f"pre_{i}",), a, b) for i, (a, b) in enumerate(zip(pre_sizes[:-1], pre_sizes[1:]))]
-    out += [(("gru", "rz"), I + H, 2 * H), (("gru", "xn"), I, H), (("gru", "hn"), H, H)]
+    if cell == "lstm":
+        out += [(("lstm",), I + H, 4 * H)]
+    else:
+        out += [(("gru", "rz"), I + H, 2 * H), (("gru", "xn"), I, H), (("gru", "hn"), H, H)]
     widths = [H] + list(post_sizes)
     out += [((f"post_{i}",), a, b) for i, (a, b) in enumerate(zip(widths[:-1], widths[1:]))]
     return out
@@ -458,14 +466,16 @@ def _gru_layout(pre_sizes, hidden, post_sizes):
 
 class RecurrentParams(dict):
     """``{"pre_i": {kernel, bias}, "gru": {"rz" | "xn" | "hn": {kernel, bias}}, "post_i": {kernel,
-    bias}}`` whose tensors are views into the flat ``theta``."""
+    bias}}`` whose tensors are views into the flat ``theta``; under ``cell="lstm"`` the cell's entry is
+    ``"lstm": {kernel (I + H, 4 H), bias (4 H)}`` (gates i, f, g, o) in place of ``"gru"``."""
 
-    def __init__(self, theta: torch.Tensor, pre_sizes, hidden, post_sizes):
+    def __init__(self, theta: torch.Tensor, pre_sizes, hidden, post_sizes, cell: str = "gru"):
         super().__init__()
         self.theta = theta
         self.pre_sizes, self.hidden, self.post_sizes = list(pre_sizes), int(hidden), list(post_sizes)
+        self.cell = cell
         off = 0
-        for path, n_in, n_out in _gru_layout(self.pre_sizes, self.hidden, self.post_sizes):
+        for path, n_in, n_out in _gru_layout(self.pre_sizes, self.hidden, self.post_sizes, cell):
             kernel = theta[off:off + n_in * n_out].view(n_in, n_out)
             off += n_in * n_out
             leaf = {"kernel": kernel, "bias": theta[off:off + n_out]}
@@ -478,7 +488,8 @@ class RecurrentParams(dict):
             raise ValueError(f"theta has {theta.numel()} elements, the network {off}")
 
     def to(self, device) -> "RecurrentParams":
-        return RecurrentParams(self.theta.detach().to(device).contiguous(), self.pre_sizes, self.hidden, self.post_sizes)
+        return RecurrentParams(self.theta.detach().to(device).contiguous(), self.pre_sizes, self.hidden, self.post_sizes,
+                               self.cell)
 
 
 @dataclasses.dataclass
@@ -493,10 +504,12 @@ class RecurrentModel:
     gru: Optional[GRUHandle] = None
     apply_sequence: Any = None          # a window of T steps in torch ops (autograd, any dtype and device)
     apply_sequence_native: Any = None   # the same window in the engine, forward and backward
+    cell: str = "gru"                   # "gru" or "lstm"
+    state_size: Optional[int] = None    # the recurrent state's width: H (gru), 2 H (lstm: [h ; c])
 
 
-def _recurrent_torch(pre, H, post, act, theta, x, h, reset):
-    """The recurrent network in torch ops on 2-D x (B, D), h (B, H)."""
+def _recurrent_torch(pre, H, post, act, theta, x, h, reset, cell="gru"):
+    """The recurrent network in torch ops on 2-D x (B, D), h (B, H) (``cell="lstm"``: (B, 2 H) = [h ; c])."""
     fn, off = _TORCH_ACT[act], 0
 
     def dense(v, n_in, n_out):
@@ -512,34 +525,51 @@ def _recurrent_torch(pre, H, post, act, theta, x, h, reset):
     I = pre[-1]
     if reset is not None:
         h = torch.where(reset.reshape(-1, 1) != 0, torch.zeros_like(h), h)
-    rz = torch.sigmoid(dense(torch.cat([x, h], dim=-1), I + H, 2 * H))
-    r, z = rz[:, :H], rz[:, H:]
-    cx = dense(x, I, H)
-    ch = dense(h, H, H)
-    n = torch.tanh(cx + r * ch)
-    h_new = n + z * (h - n)
+    if cell == "lstm":
+        a = dense(torch.cat([x, h[:, :H]], dim=-1), I + H, 4 * H)
+        ig, fg, og = torch.sigmoid(a[:, :H]), torch.sigmoid(a[:, H:2 * H]), torch.sigmoid(a[:, 3 * H:])
+        c_new = fg * h[:, H:] + ig * torch.tanh(a[:, 2 * H:3 * H])
+        h_new = og * torch.tanh(c_new)
+        state = torch.cat([h_new, c_new], dim=-1)
+    else:
+        rz = torch.sigmoid(dense(torch.cat([x, h], dim=-1), I + H, 2 * H))
+        r, z = rz[:, :H], rz[:, H:]
+        cx = dense(x, I, H)
+        ch = dense(h, H, H)
+        n = torch.tanh(cx + r * ch)
+        state = h_new = n + z * (h - n)
     y, widths = h_new, [H] + list(post)
     for i, (n_in, n_out) in enumerate(zip(widths[:-1], widths[1:])):
         y = dense(y, n_in, n_out)
         if i != len(post) - 1:
             y = fn(y)
-    return y, h_new
+    return y, state
 
 
 def make_recurrent_model(pre_sizes: Sequence[int], hidden_size: int, post_sizes: Sequence[int], obs_size: int,
-                         activation: Any = "swish") -> RecurrentModel:
+                         activation: Any = "swish", cell: str = "gru") -> RecurrentModel:
     """``obs_size -> pre_sizes (activation after every layer) -> GRU cell (hidden_size) ->
     post_sizes (activation after all but the last)``.  ``model.init(key)`` returns
     ``RecurrentParams``: one ``key, sub = split(key)`` per weight matrix in ``theta`` order (the
     pre-MLP's, W_rz, W_xn, W_hn, the post-MLP's), each lecun-uniform on its ``in``, biases zero.
     ``model.apply(params, x, h, reset=None) -> (y, h_new)``: x (B, obs_size), h (B, hidden_size),
-    reset (B,) (non-zero: the env starts from h = 0).  ``model.initial_state(B, device)``: zeros."""
+    reset (B,) (non-zero: the env starts from h = 0).  ``model.initial_state(B, device)``: zeros.
+
+    ``cell="lstm"`` swaps the cell for an LSTM (DESIGN.md "LSTM cell": ``pob_lstm_create``, the kernels
+    ``k_lstm_forward`` / ``k_lstm_policy_act``): one fused matrix W (I + H, 4 H) and bias (4 H), gates in
+    ``torch.nn.LSTMCell``'s order i, f, g, o (``weight_ih = W[:I].T``, ``weight_hh = W[I:].T``, ``bias_ih = b``,
+    ``bias_hh = 0``).  The state is then ONE tensor (B, ``model.state_size``) = (B, 2 H) = ``[h ; c]``
+    wherever the GRU carries ``h``.  ``apply`` and ``apply_sequence`` serve it; ``apply_sequence_native``
+    raises ``ValueError`` (no native BPTT for the LSTM)."""
+    if cell not in ("gru", "lstm"):
+        raise ValueError(f"cell must be 'gru' or 'lstm', got {cell!r}")
     pre = (int(obs_size),) + tuple(int(s) for s in pre_sizes)
     post = tuple(int(s) for s in post_sizes)
     H = int(hidden_size)
+    SW = 2 * H if cell == "lstm" else H  # the state's width
     act = _activation_id(activation)
-    gru = GRUHandle(pre, H, post, act)  # ValueError names the limit that is exceeded
-    layout = _gru_layout(pre, H, post)
+    gru = GRUHandle(pre, H, post, act, cell)  # ValueError names the limit that is exceeded
+    layout = _gru_layout(pre, H, post, cell)
 
     def init(key) -> RecurrentParams:
         key = _key_words(key)
@@ -555,24 +585,24 @@ def make_recurrent_model(pre_sizes: Sequence[int], hidden_size: int, post_sizes:
                 key, sub = _host_split(key)
                 w = _host_uniform(sub, n_in * n_out, -lim, lim)
             parts += [w, torch.zeros(n_out, dtype=torch.float32, device=dev)]
-        return RecurrentParams(torch.cat(parts).contiguous(), pre, H, post)
+        return RecurrentParams(torch.cat(parts).contiguous(), pre, H, post, cell)
 
     def initial_state(B: int, device=None) -> torch.Tensor:
-        return torch.zeros((int(B), H), dtype=torch.float32, device=device)
+        return torch.zeros((int(B), SW), dtype=torch.float32, device=device)
 
     def apply(params, x: torch.Tensor, h: torch.Tensor, reset: Optional[torch.Tensor] = None):
         theta = params.theta
         if theta.numel() != gru.param_count:
             raise ValueError(f"theta has {theta.numel()} elements, the network {gru.param_count}")
-        if x.dim() != 2 or x.shape[1] != pre[0] or tuple(h.shape) != (x.shape[0], H):
-            raise ValueError(f"x must be (B, {pre[0]}) and h (B, {H})")
+        if x.dim() != 2 or x.shape[1] != pre[0] or tuple(h.shape) != (x.shape[0], SW):
+            raise ValueError(f"x must be (B, {pre[0]}) and h (B, {SW})")
         if reset is not None and tuple(reset.shape) != (x.shape[0],):
             raise ValueError("reset must be (B,)")
         need_grad = torch.is_grad_enabled() and (x.requires_grad or h.requires_grad or theta.requires_grad)
         fused = (x.is_cuda and x.dtype == torch.float32 and theta.is_cuda and theta.dtype == torch.float32
                  and theta.is_contiguous() and h.is_cuda and h.dtype == torch.float32 and not need_grad)
         if not fused:
-            return _recurrent_torch(pre, H, post, act, theta, x, h, reset)
+            return _recurrent_torch(pre, H, post, act, theta, x, h, reset, cell)
         x2 = x.detach().contiguous()
         h_new = h.detach().clone(memory_format=torch.contiguous_format)
         rs = None if reset is None else reset.detach().to(torch.float32).contiguous()
@@ -595,13 +625,13 @@ def make_recurrent_model(pre_sizes: Sequence[int], hidden_size: int, post_sizes:
         if x.dim() != 3 or x.shape[2] != pre[0] or x.shape[0] < 1:
             raise ValueError(f"x must be (T, M, {pre[0]}) with T >= 1")
         T, M = int(x.shape[0]), int(x.shape[1])
-        if tuple(h0.shape) != (M, H):
-            raise ValueError(f"h0 must be ({M}, {H})")
+        if tuple(h0.shape) != (M, SW):
+            raise ValueError(f"h0 must be ({M}, {SW})")
         if reset is not None and tuple(reset.shape) != (T, M):
             raise ValueError(f"reset must be ({T}, {M})")
         h, ys = h0, []
         for t in range(T):
-            y, h = _recurrent_torch(pre, H, post, act, theta, x[t], h, None if reset is None else reset[t])
+            y, h = _recurrent_torch(pre, H, post, act, theta, x[t], h, None if reset is None else reset[t], cell)
             ys.append(y)
         return torch.stack(ys), h
 
@@ -657,6 +687,9 @@ def make_recurrent_model(pre_sizes: Sequence[int], hidden_size: int, post_sizes:
         ``h0.grad`` only when ``h0`` requires it, never a gradient to ``obs``; differentiable once.
         Anything else (the CPU, other dtypes, no gradient needed) is ``apply_sequence`` on the
         gathered, normalised rows."""
+        if cell != "gru":
+            raise ValueError(f"apply_sequence_native serves cell='gru' only (no native BPTT for cell={cell!r}): "
+                             "use apply_sequence")
         theta = getattr(params, "theta", None)
         for name, t in (("params.theta", theta), ("obs", obs), ("h0", h0)):
             if not isinstance(t, torch.Tensor):
@@ -711,7 +744,7 @@ def make_recurrent_model(pre_sizes: Sequence[int], hidden_size: int, post_sizes:
 
     return RecurrentModel(init=init, apply=apply, initial_state=initial_state, pre_sizes=pre, hidden_size=H,
                           post_sizes=post, activation=act, gru=gru, apply_sequence=apply_sequence,
-                          apply_sequence_native=apply_sequence_native)
+                          apply_sequence_native=apply_sequence_native, cell=cell, state_size=SW)
 
 
 class RecurrentTanhPolicy:
@@ -723,7 +756,11 @@ class RecurrentTanhPolicy:
     allocation, no host sync: capture-safe.  ``normalizer`` (a ``normalization.ObservationNormalizer``
     of the observation's width -- the masked columns' when the policy acts on those): the network
     sees the normalised observation (``pob_gru_policy_act_norm``, its table read at launch time);
-    ``obs_copy`` keeps the raw rows and the hidden state is never normalised."""
+    ``obs_copy`` keeps the raw rows and the hidden state is never normalised.
+
+    With a ``cell="lstm"`` model the same two entry points launch ``k_lstm_policy_act`` and ``hidden`` is
+    (B, ``state_size``) = (B, 2 H) = ``[h ; c]``; a reset row starts from +0 in all 2 H columns and
+    ``hidden_in`` of ``act_into`` is that wide too."""
 
     def __init__(self, model: RecurrentModel, params: RecurrentParams, key, total: Optional[int] = None, first: int = 0,
                  deterministic: bool = False, normalizer=None):
@@ -739,6 +776,7 @@ class RecurrentTanhPolicy:
         self.model, self.params, self.theta = model, params, theta
         self.obs_size, self.action_size = model.pre_sizes[0], model.post_sizes[-1] // 2
         self.hidden_size = model.hidden_size
+        self.state_size = model.state_size  # the width of ``hidden``: 2 H = [h ; c] for an LSTM
         self.normalizer = _normalization.attach(normalizer, self.obs_size, theta.device)
         self.key = _key_words(key).to(theta.device).clone()
         self.total, self.first = (None if total is None else int(total)), int(first)
@@ -751,7 +789,7 @@ class RecurrentTanhPolicy:
             self.action = torch.zeros((B, self.action_size), dtype=torch.float32, device=dev)
             self.raw = torch.zeros((B, self.action_size), dtype=torch.float32, device=dev)
             self.logp = torch.zeros((B,), dtype=torch.float32, device=dev)
-            self.hidden = torch.zeros((B, self.hidden_size), dtype=torch.float32, device=dev)
+            self.hidden = torch.zeros((B, self.state_size), dtype=torch.float32, device=dev)
             self.reset = torch.zeros((B,), dtype=torch.float32, device=dev)
 
     def act_into(self, obs: torch.Tensor, action: torch.Tensor, logp=None, raw=None, logits=None, obs_copy=None,
@@ -762,7 +800,7 @@ class RecurrentTanhPolicy:
         if not (obs.is_cuda and obs.dtype == torch.float32 and obs.dim() == 2 and obs.shape[1] == self.obs_size
                 and obs.is_contiguous()):
             raise ValueError(f"obs must be a contiguous float32 CUDA tensor (B, {self.obs_size})")
-        B, A, H = int(obs.shape[0]), self.action_size, self.hidden_size
+        B, A, H = int(obs.shape[0]), self.action_size, self.state_size
         self._buffers(B)
         reset = self.reset if reset is None else reset
         for t, shape in ((action, (B, A)), (logp, (B,)), (raw, (B, A)), (logits, (B, 2 * A)), (obs_copy, (B, self.obs_size)),

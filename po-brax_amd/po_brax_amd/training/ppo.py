@@ -561,6 +561,9 @@ class RecurrentPPOLearner(_DeviceLearner):
     faster natively, and the vendor-GEMM argument holds for 256-wide dense layers only.  There is no
     gradient to ``value_hidden0``.
 
+    An LSTM policy (``make_recurrent_model(..., cell="lstm")``) trains through ``"torch"`` only, from the
+    (B, 2 H) rows of ``roll.hidden[0]``: ``"auto"`` chooses it, ``"native"`` for it raises ``ValueError``.
+
     ``optimizer`` and ``permutation`` are ``PPOLearner``'s; the threefry and native permutations are over the B envs.
 
     Not brax's: advantages and value targets are the replay's, minibatches never cut a window shorter
@@ -574,13 +577,17 @@ class RecurrentPPOLearner(_DeviceLearner):
         if not isinstance(value_fn, (ValueFunction, RecurrentValueFunction)):
             raise TypeError("value_fn must be a training.ValueFunction or a training.RecurrentValueFunction")
         self.recurrent_critic = isinstance(value_fn, RecurrentValueFunction)
+        lstm = getattr(getattr(policy, "model", None), "cell", "gru") == "lstm"  # no native BPTT for it: its policy half is "torch"
         if isinstance(backward, str) and backward == "auto":
-            backward = ("native", "native") if self.recurrent_critic else ("native", "torch")
+            backward = ("torch" if lstm else "native", "native" if self.recurrent_critic else "torch")
         # "resident" names a feed-forward network's kernels: the value half, and only of a ValueFunction
         pair = self._backward_pair(
             backward, lambda pair: pair[0] != "resident" and not (pair[1] == "resident" and self.recurrent_critic),
             "backward must be 'auto', 'torch', 'native' or a (policy, value) pair of the last two "
             "(value: also 'resident' for a feed-forward ValueFunction)")
+        if lstm and pair[0] == "native":
+            raise ValueError("backward='native' for the policy needs cell='gru': an LSTM policy trains with 'torch' "
+                             "(model.apply_sequence under autograd)")
         super().__init__(policy, value_fn, pair, learning_rate, entropy_cost, ppo_epsilon, num_minibatches,
                          num_update_epochs, key, optimizer, permutation)
 

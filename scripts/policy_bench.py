@@ -21,6 +21,9 @@ no pre-MLP, one post layer of 2 A logits):
   B  rollout.RecurrentActorRollout: ONE pob_gru_policy_act launch per step
   C  rollout.GraphRollout on pre-drawn actions
 
+--cell lstm (with --recurrent) swaps the cell of all three legs' network for the LSTM of DESIGN.md
+"LSTM cell" (state (B, 2 H) = [h ; c]; leg B is then ONE k_lstm_policy_act launch per step).
+
 --masked creates the envs with the standard observability mask (30 of HH's 114 columns, fused
 into the step kernel) and both policies act on state.info["obs_masked"].
 
@@ -71,7 +74,7 @@ class TorchRecurrentPolicy:
 
     def __init__(self, model, params, B, action_size, masked):
         self.model, self.theta, self.A, self.masked = model, params.theta, action_size, masked
-        self.hidden = torch.zeros((B, model.hidden_size), device=params.theta.device)
+        self.hidden = torch.zeros((B, model.state_size), device=params.theta.device)
         self.reset = torch.zeros((B,), device=params.theta.device)
         self.tap = None
 
@@ -81,7 +84,7 @@ class TorchRecurrentPolicy:
         if self.masked:
             obs = self.tap.state.info["obs_masked"]
         y, h = _recurrent_torch(m.pre_sizes, m.hidden_size, m.post_sizes, m.activation, self.theta, obs, self.hidden,
-                                self.reset)
+                                self.reset, m.cell)
         self.hidden.copy_(h)
         loc, s = y[:, :self.A], y[:, self.A:]
         scale = torch.nn.functional.softplus(s) + 0.001
@@ -116,6 +119,7 @@ def main():
     ap.add_argument("--masked", action="store_true")
     ap.add_argument("--hidden", type=int, default=64)
     ap.add_argument("--normalize", action="store_true")
+    ap.add_argument("--cell", default="gru", choices=("gru", "lstm"))
     args = ap.parse_args()
 
     from po_brax_amd import envs, jumpy
@@ -141,7 +145,7 @@ def main():
         legs = {}
         for i, (leg, upd) in enumerate((("B", False), ("N", False), ("U", True))):
             if args.recurrent:
-                model = networks.make_recurrent_model([], args.hidden, [2 * A], D)
+                model = networks.make_recurrent_model([], args.hidden, [2 * A], D, cell=args.cell)
                 pol = networks.RecurrentTanhPolicy(model, model.init(jumpy.random_prngkey(1)), jumpy.random_prngkey(2),
                                                    normalizer=norms[i])
                 legs[leg] = RecurrentActorRollout(es[i], ss[i], pol, T, masked=args.masked, update_normalizer=upd)
@@ -152,7 +156,7 @@ def main():
                 legs[leg] = ActorRollout(es[i], ss[i], pol, T, update_normalizer=upd)
         roll_a, roll_b = None, legs["B"]
     elif args.recurrent:
-        model = networks.make_recurrent_model([], args.hidden, [2 * A], D)
+        model = networks.make_recurrent_model([], args.hidden, [2 * A], D, cell=args.cell)
         params = model.init(jumpy.random_prngkey(1))
         torch_policy = TorchRecurrentPolicy(model, params, B, A, args.masked)
         with torch.no_grad():
@@ -216,7 +220,8 @@ def main():
                 f.write(line + "\n")
         return
     res = {
-        "bench": "policy_bench", "recurrent": args.recurrent, "masked": args.masked,
+        "bench": "policy_bench", "recurrent": args.recurrent, "cell": args.cell if args.recurrent else None,
+        "masked": args.masked,
         "obs_width": D, "hidden": args.hidden if args.recurrent else None, "env": args.env, "batch": B, "steps": T, "rounds": args.rounds,
         "device": torch.cuda.get_device_name(0),
         "A_policy_rollout_torch_ms_per_step": round(med["A"], 5),
