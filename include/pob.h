@@ -399,6 +399,30 @@ int pob_mlp_forward_train_wide(const pob_mlp *mlp, long long M, const float *x, 
                                float *saved, void *stream);
 int pob_mlp_backward_wide(const pob_mlp *mlp, long long M, const float *x, const float *theta, const float *saved,
                           const float *dy, float *dtheta, float *dx /* may be NULL */, void *workspace, void *stream);
+/* The row-indexed pass (ABI v8, additive; DESIGN.md "Row-indexed training pass"): the four entries
+ * above on the rows norm.apply(x[idx]) of a trajectory array x (N, D) read in place, those rows never
+ * written anywhere; mlp_forward_train_rows_ref / mlp_backward_rows_ref of csrc/pob_mlp.h bit for bit,
+ * i.e. the bits of the plain entries on the materialised rows.  Minibatch row i is row idx[i] of x
+ * (int32, M entries, every one in [0, N): NOT checked on the device, as for pob_ppo_loss), or row i
+ * when idx is NULL (then M <= N); norm is the (3, D) normaliser table of pob_mlp_forward_norm, or NULL.
+ * The backward recomputes layer 0's input from the raw rows: x, idx, norm and norm_clip must be the
+ * forward's.  There is no gradient to x through idx or norm: with either, dx must be NULL (POB_EINVAL);
+ * with neither these ARE the plain entries.  N >= 1, M >= 1; saved and workspace sizes, the other
+ * limits, checks and the error contract are the plain entries'.  Capturable. */
+int pob_mlp_forward_train_rows(const pob_mlp *mlp, long long M, long long N, const float *x,
+                               const int32_t *idx /* may be NULL */, const float *theta, float *y, float *saved,
+                               const float *norm /* may be NULL */, float norm_clip, void *stream);
+int pob_mlp_backward_rows(const pob_mlp *mlp, long long M, long long N, const float *x,
+                          const int32_t *idx /* may be NULL */, const float *theta, const float *saved, const float *dy,
+                          float *dtheta, float *dx /* NULL with idx or norm */, const float *norm /* may be NULL */,
+                          float norm_clip, void *workspace, void *stream);
+int pob_mlp_forward_train_wide_rows(const pob_mlp *mlp, long long M, long long N, const float *x,
+                                    const int32_t *idx /* may be NULL */, const float *theta, float *y, float *saved,
+                                    const float *norm /* may be NULL */, float norm_clip, void *stream);
+int pob_mlp_backward_wide_rows(const pob_mlp *mlp, long long M, long long N, const float *x,
+                               const int32_t *idx /* may be NULL */, const float *theta, const float *saved,
+                               const float *dy, float *dtheta, float *dx /* NULL with idx or norm */,
+                               const float *norm /* may be NULL */, float norm_clip, void *workspace, void *stream);
 
 /* ---- Recurrent backward (ABI v8, additive): the training forward of a pob_gru over a window of T
  * steps and its truncated backward pass through time; gru_sequence_forward_train_ref /

@@ -624,6 +624,38 @@ static inline int mlp_backward_ref(const int n_layers, const int *sizes, const i
   free(delta); free(g); free(a);
   return 0;
 }
+// ---- the row-indexed pass (DESIGN.md "Row-indexed training pass"; pob_mlp_*_rows): minibatch row i
+// is row idx[i] (NULL: i) of x (N, D) under the normaliser table (NULL: as it is).  rows (M, D)
+// receives the gathered, normalised rows: what the kernels never write.
+static inline void mlp_rows_ref(const long long M, const int D, const float *x, const int32_t *idx, const float *table,
+                                const float clip, float *rows) {
+  for (long long i = 0; i < M; ++i)
+    for (int f = 0; f < D; ++f) rows[i * D + f] = x[(idx ? idx[i] : i) * D + f];
+  obsnorm_apply_ref(rows, M, D, table, clip);
+}
+// mlp_forward_train_ref / mlp_backward_ref on those rows (no dx); -1 when the rows cannot be allocated
+static inline int mlp_forward_train_rows_ref(const int n_layers, const int *sizes, const int activation,
+                                             const int activate_final, const long long M, const float *x, const int32_t *idx,
+                                             const float *table, const float clip, const float *theta, float *y,
+                                             float *saved) {
+  float *rows = (float *)malloc(sizeof(float) * M * sizes[0]);
+  if (!rows) return -1;
+  mlp_rows_ref(M, sizes[0], x, idx, table, clip, rows);
+  mlp_forward_train_ref(n_layers, sizes, activation, activate_final, M, rows, theta, y, saved);
+  free(rows);
+  return 0;
+}
+static inline int mlp_backward_rows_ref(const int n_layers, const int *sizes, const int activation, const int activate_final,
+                                        const long long M, const float *x, const int32_t *idx, const float *table,
+                                        const float clip, const float *theta, const float *saved, const float *dy,
+                                        float *dtheta) {
+  float *rows = (float *)malloc(sizeof(float) * M * sizes[0]);
+  if (!rows) return -1;
+  mlp_rows_ref(M, sizes[0], x, idx, table, clip, rows);
+  const int rc = mlp_backward_ref(n_layers, sizes, activation, activate_final, M, rows, theta, saved, dy, dtheta, NULL, NULL);
+  free(rows);
+  return rc;
+}
 
 // The actor on rows of logits (B, 2 A) and the uniform draws u (B, A); logp sums the terms in
 // natural order a = 0 .. A - 1 from +0.  Deterministic: action = tanh(loc), raw = loc, logp

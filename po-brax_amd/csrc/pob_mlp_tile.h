@@ -149,6 +149,79 @@ POB_MLP_D void mlp_tile_load(float *img, const float *x, const int D, const int 
   }
 }
 
+// ---- the gathering load (DESIGN.md "Row-indexed training pass"): tile row r is row idx[b0 + r] of
+// an (N, D) array read in place.  Rows are not neighbours in memory, so the lanes are dealt by row,
+// not by flat element: a GROUP of G consecutive lanes (G = 64 for D > 32, else the power of two that
+// covers D, at least LANES / ROWS) owns one row at a time and walks its columns, lane c of the group
+// taking columns c, c + G, .. (CH = ceil(D / G) <= 4 of them): every load instruction of a group is
+// one contiguous piece of one row, and a lane's column set never changes, so its mean and scale are
+// loaded once, not per element.  The block's LANES / G groups take rows g, g + LANES / G, ..
+// The tile's ROWS indices are loaded once, lane r of every wave holding idx[b0 + min(r, valid - 1)]
+// (tail rows repeat the last valid index); a group reads its row's index from that register by a
+// wave shuffle.  MLP_STAGE loads are in flight per lane: MLP_STAGE / CH rows times CH columns.
+// idx values are the caller's to keep inside [0, N): with them every element load is inside x.
+template <bool NORM, int CH, int ROWS, int LANES, int PITCH>
+POB_MLP_D void mlp_tile_gather_ch(float *img, const float *x, const int D, const int g_shift, const int my_row,
+                                  const float *norm, const float clip, const int tid) {
+  constexpr int RS = MLP_STAGE / CH;  // rows of one stage
+  const int G = 1 << g_shift, c = tid & (G - 1), g = tid >> g_shift, ng = LANES >> g_shift;
+  float mu[CH], sc[CH];
+#pragma unroll
+  for (int k = 0; k < CH; ++k) {
+    const bool cok = c + G * k < D;
+    mu[k] = (NORM && cok) ? norm[c + G * k] : 0.0f;
+    sc[k] = (NORM && cok) ? norm[D + c + G * k] : 0.0f;
+  }
+  for (int base = 0; base < ROWS; base += ng * RS) {  // the same trip count in every lane: the shuffle's sources are live
+    const int r0 = base + g;
+    float v[RS][CH];
+#pragma unroll
+    for (int u = 0; u < RS; ++u) {
+      const int row = r0 + ng * u;
+      const int src = __shfl(my_row, row < ROWS ? row : 0);  // every lane, before any branch
+#pragma unroll
+      for (int k = 0; k < CH; ++k)
+        v[u][k] = (row < ROWS && c + G * k < D) ? x[(size_t)src * D + (c + G * k)] : 0.0f;
+    }
+#pragma unroll
+    for (int u = 0; u < RS; ++u) {
+      const int row = r0 + ng * u;
+#pragma unroll
+      for (int k = 0; k < CH; ++k)
+        if (row < ROWS && c + G * k < D)
+          img[(c + G * k) * PITCH + row] = NORM ? pob_obsnorm_apply(v[u][k], mu[k], sc[k], clip) : v[u][k];
+    }
+  }
+}
+
+// features [0, D) of an image <- rows idx[b0 .. b0 + ROWS) of x (N, D); NORM as mlp_tile_load's
+template <bool NORM, int ROWS = MLP_ROWS, int LANES = 64, int PITCH = MLP_PITCH>
+POB_MLP_D void mlp_tile_gather(float *img, const float *x, const int D, const int32_t *idx, const int b0, const int valid,
+                               const float *norm, const float clip, const int tid) {
+  const int r = tid & 63;
+  const int my_row = idx[b0 + (r < valid ? r : valid - 1)];
+  int g_shift = 6;
+  if (D <= 32) {
+    g_shift = 0;
+    while ((1 << g_shift) < D) ++g_shift;
+    const int least = __builtin_ctz(LANES / ROWS);
+    g_shift = g_shift < least ? least : g_shift;
+  }
+  const int ch = (D + (1 << g_shift) - 1) >> g_shift;
+  if (ch == 1) mlp_tile_gather_ch<NORM, 1, ROWS, LANES, PITCH>(img, x, D, g_shift, my_row, norm, clip, tid);
+  else if (ch == 2) mlp_tile_gather_ch<NORM, 2, ROWS, LANES, PITCH>(img, x, D, g_shift, my_row, norm, clip, tid);
+  else if (ch == 3) mlp_tile_gather_ch<NORM, 3, ROWS, LANES, PITCH>(img, x, D, g_shift, my_row, norm, clip, tid);
+  else mlp_tile_gather_ch<NORM, 4, ROWS, LANES, PITCH>(img, x, D, g_shift, my_row, norm, clip, tid);
+}
+
+// the first image of a training forward: the contiguous load, or the gathering one where idx is given
+template <bool NORM, int ROWS = MLP_ROWS, int LANES = 64, int PITCH = MLP_PITCH>
+POB_MLP_D void mlp_tile_load_rows(float *img, const float *x, const int D, const int32_t *idx, const int b0,
+                                  const int valid, const float *norm, const float clip, const int tid) {
+  if (idx) mlp_tile_gather<NORM, ROWS, LANES, PITCH>(img, x, D, idx, b0, valid, norm, clip, tid);
+  else mlp_tile_load<NORM, ROWS, LANES, PITCH>(img, x, D, b0, valid, nullptr, nullptr, norm, clip, tid);
+}
+
 // The forward of one tile.  Returns the image holding the last layer's output.
 template <bool NORM>
 POB_MLP_D float *mlp_tile_forward(const MlpDesc &d, float *imgA, float *imgB, const int B, const int b0, const float *x,

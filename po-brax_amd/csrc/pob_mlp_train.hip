@@ -16,17 +16,23 @@
 // sixteen float64 registers and zeroed; the float64 chunk partial goes to the workspace.
 // k_mlp_bwd_reduce (pob_mlp_back.h): one lane per parameter adds the chunk partials in ascending
 // order and rounds once.  Vector stores only, no atomics, no scratch, no allocation.
+// The row-indexed pass (pob_mlp_*_rows; DESIGN.md "Row-indexed training pass") is the same kernels with
+// the first image, and the weight gradient's layer-0 operand, read as norm.apply(x[idx]) in place.
 #include "pob_mlp_back.h"
 #include "pob_mlp_wide.h"
 
-template <int H>
+// ROWS: the first image is row idx[b0 + r] of x (idx NULL: row b0 + r), normalised when NORM (the
+// row-indexed pass: DESIGN.md "Row-indexed training pass"); neither: the contiguous rows of x as they are
+template <int H, bool ROWS, bool NORM>
 __global__ __launch_bounds__(64) void k_mlp_forward_train(const MlpDesc d, const int split, const int B, const float *x,
-                                                          const float *theta, float *y, float *saved) {
+                                                          const int32_t *idx, const float *theta, float *y, float *saved,
+                                                          const float *norm, const float norm_clip) {
   __shared__ float img[H * MLP_PITCH];
   const int lane = threadIdx.x, b0 = blockIdx.x * MLP_ROWS;
   const int valid = B - b0 < MLP_ROWS ? B - b0 : MLP_ROWS;
   float *src = img, *dst = img + split * MLP_PITCH;
-  mlp_tile_load<false>(src, x, d.sizes[0], b0, valid, nullptr, nullptr, nullptr, 0.0f, lane);
+  if (ROWS) mlp_tile_load_rows<NORM>(src, x, d.sizes[0], idx, b0, valid, norm, norm_clip, lane);
+  else mlp_tile_load<false>(src, x, d.sizes[0], b0, valid, nullptr, nullptr, nullptr, 0.0f, lane);
   __syncthreads();
   const float *W = theta;
   float *sv = saved;
@@ -86,9 +92,15 @@ __global__ __launch_bounds__(64) void k_mlp_bwd_delta(const MlpDesc d, const int
   if (dx) mlp_tile_store(dx, cur, 0, d.sizes[0], b0, valid, lane);
 }
 
-__global__ __launch_bounds__(64) void k_mlp_bwd_weights(const MlpDesc d, const int B, const long long n_params,
-                                                        const float *x, const float *saved, const float *delta,
-                                                        double *partials) {
+// ROWS: layer 0's left operand is row idx[r] of x (idx NULL: row r) under the normaliser (norm NULL:
+// as it is), recomputed from the raw row with the forward's pob_obsnorm_apply: the same bits.  A
+// lane's column ai is fixed, so its mean and scale are loaded once.  A tile's 32 row indices sit in ONE
+// register, lane i (and i + 32) holding the index of row rt + i: the NEXT tile's are loaded while this
+// tile's operands are in flight, and a lane half takes its sixteen by wave shuffles.
+template <bool ROWS>
+POB_MLP_D void mlp_bwd_weights_block(const MlpDesc &d, const int B, const long long n_params, const float *x,
+                                     const int32_t *idx, const float *saved, const float *delta, double *partials,
+                                     const float *norm, const float norm_clip) {
   const int lane = threadIdx.x, j = lane & 31, h = lane >> 5;
   // blockIdx.y counts the 32 x 32 tiles of the layers' (in + 1, out) blocks, layer by layer
   int t = blockIdx.y, l = 0, tj;
@@ -112,14 +124,38 @@ __global__ __launch_bounds__(64) void k_mlp_bwd_weights(const MlpDesc d, const i
   double sum[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) sum[r] = 0.0;
+  const bool gather = ROWS && l == 0;
+  float mu = 0.0f, sc = 0.0f;
+  int src = 0;  // the row of x behind row rt + j of the tile at hand (a row past the chunk: its last row's)
+  if (gather) {
+    if (norm && a_ok) { mu = norm[ai]; sc = norm[in + ai]; }
+    const int row = r_begin + j < r_end ? r_begin + j : r_end - 1;
+    src = idx ? idx[row] : row;
+  }
   for (int rt = r_begin; rt < r_end; rt += 32) {
     float a[16], b[16];
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
       const int row = rt + mlp_kfeat(u, h);
       const bool rok = row < r_end;
-      a[u] = (rok && a_ok) ? A[(size_t)row * in + ai] : 0.0f;
+      if (gather) {
+        const int s = __shfl(src, mlp_kfeat(u, h));  // every lane, before the branch
+        a[u] = (rok && a_ok) ? A[(size_t)s * in + ai] : 0.0f;
+      } else {
+        a[u] = (rok && a_ok) ? A[(size_t)row * in + ai] : 0.0f;
+      }
       b[u] = (rok && b_ok) ? D[(size_t)row * out + bj] : 0.0f;
+    }
+    if (gather) {
+      const int row = rt + 32 + j < r_end ? rt + 32 + j : r_end - 1;  // the next tile's indices, under this tile's loads
+      src = idx ? idx[row] : row;
+      if (norm) {
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+          const float v = pob_obsnorm_apply(a[u], mu, sc, norm_clip);
+          a[u] = (rt + mlp_kfeat(u, h) < r_end && a_ok) ? v : 0.0f;
+        }
+      }
     }
     if (l) {
 #pragma unroll
@@ -146,6 +182,19 @@ __global__ __launch_bounds__(64) void k_mlp_bwd_weights(const MlpDesc d, const i
     const int i = (t / tj) * 32 + mlp_acc_row(r, h);
     if (i <= in && b_ok) P[(size_t)i * out + bj] = sum[r];
   }
+}
+
+__global__ __launch_bounds__(64) void k_mlp_bwd_weights(const MlpDesc d, const int B, const long long n_params,
+                                                        const float *x, const float *saved, const float *delta,
+                                                        double *partials) {
+  mlp_bwd_weights_block<false>(d, B, n_params, x, nullptr, saved, delta, partials, nullptr, 0.0f);
+}
+
+// held to the plain kernel's four waves a SIMD
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void k_mlp_bwd_weights_rows(
+    const MlpDesc d, const int B, const long long n_params, const float *x, const int32_t *idx, const float *saved,
+    const float *delta, double *partials, const float *norm, const float norm_clip) {
+  mlp_bwd_weights_block<true>(d, B, n_params, x, idx, saved, delta, partials, norm, norm_clip);
 }
 
 // ============================================================================ wide training pass
@@ -214,13 +263,19 @@ struct mlpw_walk {
   }
 };
 
+// idx, norm: the row-indexed pass (k_mlp_forward_train<H, true, NORM>'s first image in this layout), chosen
+// at run time, uniformly, before the layers: ONE kernel, since the layers' functions are calls here and a
+// second kernel calling them costs this one, at 256 VGPRs, four spilled registers
 __global__ __launch_bounds__(MLPW_LANES, 2) __attribute__((target("no-packed-fp32-ops"))) void k_mlp_forward_train_wide(
-    const MlpDesc d, const int B, const float *x, const float *theta, float *y, float *saved) {
+    const MlpDesc d, const int B, const float *x, const int32_t *idx, const float *theta, float *y, float *saved,
+    const float *norm, const float norm_clip) {
   __shared__ float img[POB_MLP_MAX_WIDTH * MLPW_PITCH];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int b0 = blockIdx.x * MLPW_ROWS;
   const int valid = B - b0 < MLPW_ROWS ? B - b0 : MLPW_ROWS;
-  mlp_tile_load<false, MLPW_ROWS, MLPW_LANES, MLPW_PITCH>(img, x, d.sizes[0], b0, valid, nullptr, nullptr, nullptr, 0.0f, tid);
+  if (norm) mlp_tile_load_rows<true, MLPW_ROWS, MLPW_LANES, MLPW_PITCH>(img, x, d.sizes[0], idx, b0, valid, norm, norm_clip, tid);
+  else if (idx) mlp_tile_gather<false, MLPW_ROWS, MLPW_LANES, MLPW_PITCH>(img, x, d.sizes[0], idx, b0, valid, nullptr, 0.0f, tid);
+  else mlp_tile_load<false, MLPW_ROWS, MLPW_LANES, MLPW_PITCH>(img, x, d.sizes[0], b0, valid, nullptr, nullptr, nullptr, 0.0f, tid);
   mlpw_barrier();
   const float *W = theta;
   float *sv = saved;
@@ -419,9 +474,21 @@ static unsigned mlp_weight_tiles(const MlpDesc &d) {
   return tiles;
 }
 
-// pob_mlp_forward_train and its four-wave form
-static int mlp_forward_train(const pob_mlp *m, long long M, const float *x, const float *theta, float *y, float *saved,
-                             bool wide, void *stream) {
+// the template arguments after the pool height of k_mlp_forward_train (TILE_DISPATCH_T's N)
+#define TILE_TARG_plain , false, false
+#define TILE_TARG_rows , true, false
+#define TILE_TARG_rows_norm , true, true
+
+// the row-indexed entries' own checks: x is (N, D); without idx the M rows are its first ones
+static int mlp_rows_check(long long M, long long N, const int32_t *idx) {
+  if (N < 1) return pob_fail_msg(POB_EINVAL, "mlp: the row count N of x must be positive");
+  if (!idx && M > N) return pob_fail_msg(POB_EINVAL, "mlp: without idx the M rows are x's first: M must not exceed N");
+  return POB_OK;
+}
+
+// pob_mlp_forward_train and its four-wave form; idx, norm: the row-indexed pass (both NULL: the plain one)
+static int mlp_forward_train(const pob_mlp *m, long long M, const float *x, const int32_t *idx, const float *theta, float *y,
+                             float *saved, const float *norm, float norm_clip, bool wide, void *stream) {
   long long n_saved, n_delta;
   const int rc = mlp_bwd_counts(m, M, &n_saved, &n_delta);
   if (rc != POB_OK) return rc;
@@ -429,25 +496,31 @@ static int mlp_forward_train(const pob_mlp *m, long long M, const float *x, cons
   const int B = (int)M;
   hipStream_t st = (hipStream_t)stream;
   if (wide) {
-    hipLaunchKernelGGL(k_mlp_forward_train_wide, mlpw_grid(M), dim3(MLPW_LANES), 0, st, m->d, B, x, theta, y, saved);
+    hipLaunchKernelGGL(k_mlp_forward_train_wide, mlpw_grid(M), dim3(MLPW_LANES), 0, st, m->d, B, x, idx, theta, y, saved, norm,
+                       norm_clip);
     return mlp_hip_check(hipGetLastError(), "k_mlp_forward_train_wide launch");
   }
   int split;
   const int cls = image_rows(m->d, false, split);
   const dim3 grid = mlp_tile_grid(M);
-  TILE_DISPATCH_T(k_mlp_forward_train, , cls, MLP_HEIGHTS, m->d, split, B, x, theta, y, saved)
+  if (norm) { TILE_DISPATCH_T(k_mlp_forward_train, rows_norm, cls, MLP_HEIGHTS, m->d, split, B, x, idx, theta, y, saved, norm, norm_clip) }
+  else if (idx) { TILE_DISPATCH_T(k_mlp_forward_train, rows, cls, MLP_HEIGHTS, m->d, split, B, x, idx, theta, y, saved, norm, norm_clip) }
+  else { TILE_DISPATCH_T(k_mlp_forward_train, plain, cls, MLP_HEIGHTS, m->d, split, B, x, idx, theta, y, saved, norm, norm_clip) }
   return mlp_hip_check(hipGetLastError(), "k_mlp_forward_train launch");
 }
 
 // pob_mlp_backward and its four-wave form: the delta kernel of the layout asked for, then the
-// parameter gradient from the same delta arrays by the same two kernels
-static int mlp_backward(const pob_mlp *m, long long M, const float *x, const float *theta, const float *saved,
-                        const float *dy, float *dtheta, float *dx, void *workspace, bool wide, void *stream) {
+// parameter gradient from the same delta arrays by the same two kernels; idx, norm: layer 0's
+// left operand gathered and normalised as the forward's was (then there is no dx)
+static int mlp_backward(const pob_mlp *m, long long M, const float *x, const int32_t *idx, const float *theta,
+                        const float *saved, const float *dy, float *dtheta, float *dx, const float *norm, float norm_clip,
+                        void *workspace, bool wide, void *stream) {
   long long n_saved, n_delta;
   const int rc = mlp_bwd_counts(m, M, &n_saved, &n_delta);
   if (rc != POB_OK) return rc;
   if (!x || !theta || !dy || !dtheta || !workspace || (n_saved && !saved))
     return pob_fail_msg(POB_EINVAL, "mlp: NULL argument (x, theta, saved, dy, dtheta, workspace)");
+  if (dx && (idx || norm)) return pob_fail_msg(POB_EINVAL, "mlp: no dx through idx or norm (pass dx = NULL)");
   const int B = (int)M;
   const long long n_chunks = (M + POB_MLP_BWD_CHUNK - 1) / POB_MLP_BWD_CHUNK;
   float *delta = (float *)workspace;
@@ -461,8 +534,12 @@ static int mlp_backward(const pob_mlp *m, long long M, const float *x, const flo
     const dim3 grid = mlp_tile_grid(M);
     TILE_DISPATCH_T(k_mlp_bwd_delta, , cls, MLP_HEIGHTS, m->d, split, B, theta, saved, dy, delta, dx)
   }
-  hipLaunchKernelGGL(k_mlp_bwd_weights, dim3((unsigned)n_chunks, mlp_weight_tiles(m->d)), dim3(64), 0, st, m->d, B, m->n_params,
-                     x, saved, (const float *)delta, partials);
+  const dim3 wgrid((unsigned)n_chunks, mlp_weight_tiles(m->d));
+  if (idx || norm)
+    hipLaunchKernelGGL(k_mlp_bwd_weights_rows, wgrid, dim3(64), 0, st, m->d, B, m->n_params, x, idx, saved, (const float *)delta,
+                       partials, norm, norm_clip);
+  else
+    hipLaunchKernelGGL(k_mlp_bwd_weights, wgrid, dim3(64), 0, st, m->d, B, m->n_params, x, saved, (const float *)delta, partials);
   hipLaunchKernelGGL(k_mlp_bwd_reduce, dim3((unsigned)((m->n_params + 255) / 256)), dim3(256), 0, st,
                      (const double *)partials, n_chunks, m->n_params, dtheta);
   return mlp_hip_check(hipGetLastError(), wide ? "k_mlp_bwd_wide launch" : "k_mlp_bwd launch");
@@ -481,7 +558,7 @@ int pob_mlp_saved_bytes(const pob_mlp *m, long long M, long long *bytes) {
 
 int pob_mlp_forward_train(const pob_mlp *m, long long M, const float *x, const float *theta, float *y, float *saved,
                           void *stream) {
-  return mlp_forward_train(m, M, x, theta, y, saved, false, stream);
+  return mlp_forward_train(m, M, x, nullptr, theta, y, saved, nullptr, 0.0f, false, stream);
 }
 
 int pob_mlp_backward_workspace_bytes(const pob_mlp *m, long long M, long long *bytes) {
@@ -497,17 +574,45 @@ int pob_mlp_backward_workspace_bytes(const pob_mlp *m, long long M, long long *b
 
 int pob_mlp_backward(const pob_mlp *m, long long M, const float *x, const float *theta, const float *saved,
                      const float *dy, float *dtheta, float *dx, void *workspace, void *stream) {
-  return mlp_backward(m, M, x, theta, saved, dy, dtheta, dx, workspace, false, stream);
+  return mlp_backward(m, M, x, nullptr, theta, saved, dy, dtheta, dx, nullptr, 0.0f, workspace, false, stream);
 }
 
 int pob_mlp_forward_train_wide(const pob_mlp *m, long long M, const float *x, const float *theta, float *y, float *saved,
                                void *stream) {
-  return mlp_forward_train(m, M, x, theta, y, saved, true, stream);
+  return mlp_forward_train(m, M, x, nullptr, theta, y, saved, nullptr, 0.0f, true, stream);
 }
 
 int pob_mlp_backward_wide(const pob_mlp *m, long long M, const float *x, const float *theta, const float *saved,
                           const float *dy, float *dtheta, float *dx, void *workspace, void *stream) {
-  return mlp_backward(m, M, x, theta, saved, dy, dtheta, dx, workspace, true, stream);
+  return mlp_backward(m, M, x, nullptr, theta, saved, dy, dtheta, dx, nullptr, 0.0f, workspace, true, stream);
+}
+
+// ---- the row-indexed pass (DESIGN.md "Row-indexed training pass")
+int pob_mlp_forward_train_rows(const pob_mlp *m, long long M, long long N, const float *x, const int32_t *idx,
+                               const float *theta, float *y, float *saved, const float *norm, float norm_clip, void *stream) {
+  const int rc = mlp_rows_check(M, N, idx);
+  return rc != POB_OK ? rc : mlp_forward_train(m, M, x, idx, theta, y, saved, norm, norm_clip, false, stream);
+}
+
+int pob_mlp_backward_rows(const pob_mlp *m, long long M, long long N, const float *x, const int32_t *idx, const float *theta,
+                          const float *saved, const float *dy, float *dtheta, float *dx, const float *norm, float norm_clip,
+                          void *workspace, void *stream) {
+  const int rc = mlp_rows_check(M, N, idx);
+  return rc != POB_OK ? rc : mlp_backward(m, M, x, idx, theta, saved, dy, dtheta, dx, norm, norm_clip, workspace, false, stream);
+}
+
+int pob_mlp_forward_train_wide_rows(const pob_mlp *m, long long M, long long N, const float *x, const int32_t *idx,
+                                    const float *theta, float *y, float *saved, const float *norm, float norm_clip,
+                                    void *stream) {
+  const int rc = mlp_rows_check(M, N, idx);
+  return rc != POB_OK ? rc : mlp_forward_train(m, M, x, idx, theta, y, saved, norm, norm_clip, true, stream);
+}
+
+int pob_mlp_backward_wide_rows(const pob_mlp *m, long long M, long long N, const float *x, const int32_t *idx,
+                               const float *theta, const float *saved, const float *dy, float *dtheta, float *dx,
+                               const float *norm, float norm_clip, void *workspace, void *stream) {
+  const int rc = mlp_rows_check(M, N, idx);
+  return rc != POB_OK ? rc : mlp_backward(m, M, x, idx, theta, saved, dy, dtheta, dx, norm, norm_clip, workspace, true, stream);
 }
 
 }  // extern "C"

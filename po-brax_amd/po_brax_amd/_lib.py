@@ -82,6 +82,7 @@ EXPORTS = (
     "pob_mlp_forward_train_wide", "pob_mlp_backward_wide",
     "pob_sort_workspace_bytes", "pob_sort_pairs_u32", "pob_random_permutation",
     "pob_mlp_bf16_workspace_bytes", "pob_mlp_forward_bf16", "pob_mlp_forward_bf16_norm",
+    "pob_mlp_forward_train_rows", "pob_mlp_backward_rows", "pob_mlp_forward_train_wide_rows", "pob_mlp_backward_wide_rows",
 )
 MLP_WIDE_ROWS = 64  # MLPW_ROWS: the rows a block of k_mlp_forward_wide owns
 SORT_TILE = 2048  # POB_SORT_TILE: the elements a block of the radix sort owns
@@ -167,6 +168,13 @@ def _load():
     lib.pob_mlp_backward.argtypes = [_VP, C.c_longlong, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]
     lib.pob_mlp_forward_train_wide.argtypes = lib.pob_mlp_forward_train.argtypes
     lib.pob_mlp_backward_wide.argtypes = lib.pob_mlp_backward.argtypes
+    # mlp, M, N, x, idx, theta, y, saved, norm, norm_clip, stream
+    lib.pob_mlp_forward_train_rows.argtypes = [_VP, C.c_longlong, C.c_longlong, _VP, _VP, _VP, _VP, _VP, _VP, C.c_float, _VP]
+    # mlp, M, N, x, idx, theta, saved, dy, dtheta, dx, norm, norm_clip, workspace, stream
+    lib.pob_mlp_backward_rows.argtypes = [_VP, C.c_longlong, C.c_longlong, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_float,
+                                          _VP, _VP]
+    lib.pob_mlp_forward_train_wide_rows.argtypes = lib.pob_mlp_forward_train_rows.argtypes
+    lib.pob_mlp_backward_wide_rows.argtypes = lib.pob_mlp_backward_rows.argtypes
     lib.pob_gru_sequence_saved_bytes.argtypes = [_VP, C.c_int, C.c_longlong, C.POINTER(C.c_longlong)]
     lib.pob_gru_sequence_backward_workspace_bytes.argtypes = [_VP, C.c_int, C.c_longlong, C.POINTER(C.c_longlong)]
     # gru, T, M, B, obs, idx, h0, reset, theta, y, h_last, saved, norm, norm_clip, stream

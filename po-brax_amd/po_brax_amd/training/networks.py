@@ -266,6 +266,8 @@ FORWARD_KERNELS = {"tile": "pob_mlp_forward", "resident": "pob_mlp_forward_wide"
 # the training pass under the same names: (forward with the pre-activations kept, backward)
 TRAIN_KERNELS = {"tile": ("pob_mlp_forward_train", "pob_mlp_backward"),
                  "resident": ("pob_mlp_forward_train_wide", "pob_mlp_backward_wide")}
+# the row-indexed pass (DESIGN.md "Row-indexed training pass"): the same pair reading norm.apply(x[idx]) in place
+TRAIN_ROWS_KERNELS = {name: tuple(entry + "_rows" for entry in pair) for name, pair in TRAIN_KERNELS.items()}
 
 
 def forward_entry(kernel: str, norm: bool = False):
@@ -279,12 +281,13 @@ def forward_entry(kernel: str, norm: bool = False):
     return getattr(lib, FORWARD_KERNELS[kernel] + ("_norm" if norm else ""))
 
 
-def train_entries(kernel: str):
+def train_entries(kernel: str, rows: bool = False):
     """The training pass's two entry points under ``forward_entry``'s names: ``"tile"`` (one wave per 32
-    rows) or ``"resident"`` (four waves per 64 rows: DESIGN.md "Wide training pass").  The same bits."""
+    rows) or ``"resident"`` (four waves per 64 rows: DESIGN.md "Wide training pass").  The same bits.
+    ``rows``: the row-indexed pair (``pob_mlp_*_rows``: DESIGN.md "Row-indexed training pass")."""
     if kernel not in TRAIN_KERNELS:
         raise ValueError(f"kernel must be one of {sorted(TRAIN_KERNELS)}, got {kernel!r}")
-    return tuple(getattr(lib, name) for name in TRAIN_KERNELS[kernel])
+    return tuple(getattr(lib, name) for name in (TRAIN_ROWS_KERNELS if rows else TRAIN_KERNELS)[kernel])
 
 
 def make_model(layer_sizes: Sequence[int], obs_size: int, activation: Any = "swish",
@@ -370,7 +373,43 @@ def make_model(layer_sizes: Sequence[int], obs_size: int, activation: Any = "swi
                                      ptr(workspace), _lib.stream_handle(dev)))
             return (dtheta if ctx.needs_input_grad[0] else None), dx, None
 
-    def apply_native(params, x: torch.Tensor, kernel: str = "tile") -> torch.Tensor:
+    class _NativeMLPRows(torch.autograd.Function):
+        """``_NativeMLP`` on rows read in place: x (N, sizes[0]) contiguous float32 CUDA, idx int32 (M,) or None
+        (then M = N), table (3, sizes[0]) or None; entries: ``train_entries(kernel, rows=True)``.  No x.grad."""
+
+        @staticmethod
+        def forward(ctx, theta, x, idx, table, clip, entries):
+            M, N, dev = int(x.shape[0] if idx is None else idx.shape[0]), int(x.shape[0]), x.device
+            need = C.c_longlong()
+            check(lib.pob_mlp_saved_bytes(mlp.handle, M, C.byref(need)))
+            saved = torch.empty(need.value // 4, dtype=torch.float32, device=dev)
+            y = torch.empty((M, sizes[-1]), dtype=torch.float32, device=dev)
+            check(entries[0](mlp.handle, M, N, ptr(x), ptr(idx), ptr(theta), ptr(y), ptr(saved), ptr(table), clip,
+                             _lib.stream_handle(dev)))
+            ctx.save_for_backward(theta, x, saved)  # x is the caller's array, not a copy of the rows
+            ctx.rows, ctx.backward_entry = (idx, table, clip, M, N), entries[1]
+            return y
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, dy):
+            theta, x, saved = ctx.saved_tensors
+            idx, table, clip, M, N = ctx.rows
+            dy = dy.contiguous()
+            need = C.c_longlong()
+            check(lib.pob_mlp_backward_workspace_bytes(mlp.handle, M, C.byref(need)))
+            workspace = torch.empty(need.value // 8, dtype=torch.float64, device=x.device)
+            dtheta = torch.empty_like(theta)
+            check(ctx.backward_entry(mlp.handle, M, N, ptr(x), ptr(idx), ptr(theta), ptr(saved), ptr(dy), ptr(dtheta), None,
+                                     ptr(table), clip, ptr(workspace), _lib.stream_handle(x.device)))
+            return (dtheta if ctx.needs_input_grad[0] else None), None, None, None, None, None
+
+    def _rows_torch(x, idx, normalizer):
+        rows = x if idx is None else x.index_select(0, idx)
+        return rows if normalizer is None else normalizer.apply(rows)
+
+    def apply_native(params, x: torch.Tensor, kernel: str = "tile", idx: Optional[torch.Tensor] = None,
+                     normalizer=None) -> torch.Tensor:
         """``apply`` whose backward pass runs in the engine as well: for a ``Params`` (or a namespace
         with ``.theta``) whose ``theta`` is a contiguous float32 CUDA tensor and a float32 CUDA ``x``,
         the forward is ``pob_mlp_forward_train`` (``apply``'s fused bits, the pre-activations kept)
@@ -383,24 +422,54 @@ def make_model(layer_sizes: Sequence[int], obs_size: int, activation: Any = "swi
         ``kernel="mixed"`` is another function, the mixed-precision training pass (DESIGN.md "Mixed training
         pass": f32 master weights, bf16 operands, f32 sums): the values of ``apply(kernel="bf16")``, which it is
         without grad, and under grad the definition in torch ops.  It has no kernels yet: where the engine's
-        backward would run (contiguous float32 CUDA ``theta`` and ``x``) it raises ``NotImplementedError``."""
+        backward would run (contiguous float32 CUDA ``theta`` and ``x``) it raises ``NotImplementedError``.
+
+        ``idx`` and ``normalizer`` make it the row-indexed pass (DESIGN.md "Row-indexed training pass"): the
+        function ``apply_native(params, normalizer.apply(x[idx]))`` and its bits, with ``x`` the whole (N,
+        obs_size) array read in place through ``idx`` (int32 (M,) on ``x``'s device, every entry in [0, N): not
+        checked on the device; None: every row) and the ``ObservationNormalizer``'s table applied in the
+        kernels' loads (``pob_mlp_forward_train_rows`` / ``pob_mlp_backward_rows`` and their ``_wide`` forms): the
+        (M, obs_size) minibatch is never written.  The result is (M, out).  There is no gradient to ``x`` on this
+        route (``x.requires_grad`` raises ``ValueError``), and ``kernel="mixed"`` does not take it.  Where the
+        kernels do not run it is ``apply`` on the gathered, normalised rows in torch ops."""
         mixed = kernel == "mixed"
-        entries = None if mixed else train_entries(kernel)
+        rows = idx is not None or normalizer is not None
+        entries = None if mixed else train_entries(kernel, rows)
+        if rows:
+            if mixed:
+                raise ValueError("kernel=\"mixed\" does not take idx or normalizer")
+            if x.requires_grad:
+                raise ValueError("no gradient to x through idx or normalizer: pass x without requires_grad")
+            if x.dim() != 2 or x.shape[1] != sizes[0]:
+                raise ValueError(f"with idx or normalizer x must be the whole (N, {sizes[0]}) array")
+            if idx is not None and not (isinstance(idx, torch.Tensor) and idx.dtype == torch.int32 and idx.dim() == 1
+                                        and idx.device == x.device):
+                raise ValueError(f"idx must be an int32 tensor (M,) on {x.device}")
+            if normalizer is not None and not callable(getattr(normalizer, "apply", None)):
+                raise TypeError("normalizer must be a normalization.ObservationNormalizer (or have its apply)")
         theta = getattr(params, "theta", None)
         need_grad = torch.is_grad_enabled() and (x.requires_grad or (
             theta.requires_grad if theta is not None else any(t.requires_grad for p in params.values() for t in p.values())))
         if not need_grad:
-            return apply(params, x, "bf16" if mixed else kernel)
+            return apply(params, _rows_torch(x, idx, normalizer) if rows else x, "bf16" if mixed else kernel)
         native = (theta is not None and x.is_cuda and x.dtype == torch.float32 and theta.is_cuda
                   and theta.dtype == torch.float32 and theta.is_contiguous() and x.numel() > 0)
+        table = getattr(normalizer, "table", None)  # the kernels read the table; anything else only has apply
+        if rows and native:
+            native = ((idx is None or idx.numel() > 0) and (normalizer is None or (
+                isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.float32
+                and table.is_contiguous() and tuple(table.shape) == (3, sizes[0]))))
         if not native:
-            return (_mixed_torch if mixed else _forward_torch)(sizes, act, params, x)
+            return (_mixed_torch if mixed else _forward_torch)(sizes, act, params, _rows_torch(x, idx, normalizer) if rows else x)
         if mixed:
             raise NotImplementedError("kernel=\"mixed\" has no native training pass (DESIGN.md \"Mixed training pass\")")
         if theta.numel() != mlp.param_count:
             raise ValueError(f"theta has {theta.numel()} elements, the network {mlp.param_count}")
         if x.shape[-1] != sizes[0]:
             raise ValueError(f"x must be (..., {sizes[0]})")
+        if rows:
+            return _NativeMLPRows.apply(theta, x.contiguous(), None if idx is None else idx.contiguous(), table,
+                                        float(normalizer.clip) if normalizer is not None else 0.0, entries)
         y = _NativeMLP.apply(theta, x.reshape(-1, sizes[0]).contiguous(), entries)
         return y.reshape(*x.shape[:-1], sizes[-1])
 
