@@ -470,6 +470,30 @@ int pob_gru_sequence_forward(const pob_gru *g, int S, long long M, long long B, 
                              float *y /* (S, M, out) */, float *h_first /* (M, H), may be NULL */,
                              float *h_out /* (M, H), may be NULL */, int h_out_step,
                              const float *norm /* may be NULL */, float norm_clip, void *stream);
+/* The same window with bf16 operands on the matrix cores and f32 accumulation (ABI v8, additive;
+ * DESIGN.md "Bf16 recurrent window"): the opt-in mixed-precision pass of the recurrent critic.  The
+ * network and the step loop are pob_gru_sequence_forward's; every operand of a matrix product is
+ * rounded to bf16 (nearest even) where it enters the product -- the normalised observation row,
+ * every weight matrix, the dense layers' hidden activations, h where it enters the r, z and
+ * candidate products -- and everything else is f32: accumulators from the f32 bias, activations,
+ * gates, n = tanh(cx + r ch), and the blend h' = n + z (h - n) on the unrounded h.  The carried state
+ * (h0, h_first, h_out) is f32 and never rounded.  The summation order is the matrix instruction's:
+ * deterministic, NOT gru_sequence_forward_ref's fmaf chain; held to a float64 statement of this
+ * definition within a tolerance.  Every call first packs theta's matrices as bf16 into `workspace`
+ * (caller-owned device memory, 16-byte aligned, pob_gru_sequence_bf16_workspace_bytes, contents
+ * irrelevant between calls) on the same stream, so theta is read at launch time.  Every gru-cell
+ * network pob_gru_create accepts; an lstm handle is POB_EINVAL.  Arguments, aliasing rules and the
+ * error contract are pob_gru_sequence_forward's, a NULL workspace rejected as the other pointers
+ * are; no allocation, no atomics, no synchronisation: capturable.
+ * pob_gru_sequence_bf16_workspace_bytes makes no HIP call. */
+int pob_gru_sequence_bf16_workspace_bytes(const pob_gru *g, long long *bytes);
+int pob_gru_sequence_forward_bf16(const pob_gru *g, int S, long long M, long long B, const float *obs,
+                                  const int32_t *idx /* may be NULL */, const float *h0,
+                                  const float *reset /* (S, B), may be NULL */, const float *theta,
+                                  float *y /* (S, M, out) */, float *h_first /* (M, H), may be NULL */,
+                                  float *h_out /* (M, H), may be NULL */, int h_out_step,
+                                  const float *norm /* may be NULL */, float norm_clip, void *workspace,
+                                  void *stream);
 
 /* ---- Fused Adam (ABI v8, additive): one optimiser step of up to POB_ADAM_MAX_SEG parameter
  * vectors in one launch, adam_step_ref of csrc/pob_mlp.h bit for bit (DESIGN.md "Learner on the

@@ -83,6 +83,7 @@ EXPORTS = (
     "pob_sort_workspace_bytes", "pob_sort_pairs_u32", "pob_random_permutation",
     "pob_mlp_bf16_workspace_bytes", "pob_mlp_forward_bf16", "pob_mlp_forward_bf16_norm",
     "pob_mlp_forward_train_rows", "pob_mlp_backward_rows", "pob_mlp_forward_train_wide_rows", "pob_mlp_backward_wide_rows",
+    "pob_gru_sequence_bf16_workspace_bytes", "pob_gru_sequence_forward_bf16",
 )
 MLP_WIDE_ROWS = 64  # MLPW_ROWS: the rows a block of k_mlp_forward_wide owns
 SORT_TILE = 2048  # POB_SORT_TILE: the elements a block of the radix sort owns
@@ -186,6 +187,9 @@ def _load():
     # gru, S, M, B, obs, idx, h0, reset, theta, y, h_first, h_out, h_out_step, norm, norm_clip, stream
     lib.pob_gru_sequence_forward.argtypes = [_VP, C.c_int, C.c_longlong, C.c_longlong, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                              _VP, C.c_int, _VP, C.c_float, _VP]
+    # the bf16 window: the same list with the workspace before the stream
+    lib.pob_gru_sequence_bf16_workspace_bytes.argtypes = [_VP, C.POINTER(C.c_longlong)]
+    lib.pob_gru_sequence_forward_bf16.argtypes = list(lib.pob_gru_sequence_forward.argtypes[:-1]) + [_VP, _VP]
     # segs (host array), n_seg, state, lr, beta1, beta2, eps, stream
     lib.pob_adam_step.argtypes = [C.POINTER(pob_adam_seg), C.c_int, _VP, C.c_float, C.c_float, C.c_float, C.c_float, _VP]
     lib.pob_sort_workspace_bytes.argtypes = [C.c_longlong]

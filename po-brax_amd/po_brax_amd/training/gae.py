@@ -23,7 +23,8 @@ import torch
 from .. import _lib
 from .._lib import check, lib, ptr
 from . import normalization as _normalization
-from .networks import FeedForwardModel, Params, RecurrentModel, RecurrentParams, bf16_workspace, forward_entry
+from .networks import (FeedForwardModel, Params, RecurrentModel, RecurrentParams, bf16_workspace, forward_entry,
+                       gru_bf16_workspace, sequence_kernel)
 
 
 def _gae_torch(truncation, termination, rewards, values, bootstrap_value, lambda_, discount, reward_scaling, vs, adv):
@@ -170,9 +171,13 @@ class RecurrentValueFunction:
     ``reset`` (B,): where it is non-zero the env's next window starts from h = 0.  Both are allocated at
     first use and start as zeros (``RecurrentTanhPolicy``'s rule); after that no allocation and no host
     sync: capture-safe.  ``params.theta`` and the table of ``normalizer`` are read at launch time, as
-    ``ValueFunction``'s."""
+    ``ValueFunction``'s.  ``kernel="bf16"`` makes the launch ``pob_gru_sequence_forward_bf16``: the
+    mixed-precision window (bf16 operands on the matrix cores, f32 accumulation, the carried state f32 and
+    unrounded: other values, DESIGN.md "Bf16 recurrent window"), its workspace owned by this object; the
+    values feed GAE only, the learner recomputes them in f32 from the same ``hidden``."""
 
-    def __init__(self, model: RecurrentModel, params: RecurrentParams, normalizer=None):
+    def __init__(self, model: RecurrentModel, params: RecurrentParams, normalizer=None, kernel: str = "tile"):
+        self.kernel = sequence_kernel(kernel)
         if getattr(model, "gru", None) is None or getattr(model, "post_sizes", None) is None:
             raise ValueError("model must come from make_recurrent_model")
         if getattr(model, "cell", "gru") != "gru":
@@ -188,6 +193,8 @@ class RecurrentValueFunction:
             raise ValueError(f"theta has {theta.numel()} elements, the network {model.gru.param_count}")
         self.model, self.params, self.theta = model, params, theta
         self.hidden = self.reset = None
+        # the bf16 window's packed weights: allocated once, here, so that values_sequence_into never allocates
+        self.workspace = gru_bf16_workspace(model.gru, theta.device) if kernel == "bf16" else None
 
     def _buffers(self, B: int):
         if self.hidden is None or self.hidden.shape[0] != B:
@@ -199,7 +206,8 @@ class RecurrentValueFunction:
                              h_first: Optional[torch.Tensor] = None, carry_step: Optional[int] = None) -> torch.Tensor:
         """``values`` (S, B) <- the value of every row of ``obs`` (S, B, D) in time order, env b starting
         from ``self.hidden[b]`` and from h = 0 at every step s with ``reset[s][b] != 0`` (reset (S, B)):
-        ONE ``pob_gru_sequence_forward`` launch.  ``h_first`` (B, H) receives the state row 0 started from,
+        ONE ``pob_gru_sequence_forward`` launch (``kernel="bf16"``: ``pob_gru_sequence_forward_bf16``, its pack pass
+        in front).  ``h_first`` (B, H) receives the state row 0 started from,
         after ``reset[0]``; ``self.hidden`` is overwritten in place with the state after ``carry_step``
         steps (1 .. S; None: S).  All contiguous float32 tensors on the parameters' device."""
         dev, D, H = self.theta.device, self.obs_size, self.hidden_size
@@ -220,8 +228,10 @@ class RecurrentValueFunction:
             raise ValueError(f"carry_step must be in 1 .. {S}, got {carry_step}")
         self._buffers(B)
         norm = self.normalizer
-        check(lib.pob_gru_sequence_forward(self.model.gru.handle, S, B, B, ptr(obs), None, ptr(self.hidden), ptr(reset),
-                                           ptr(self.theta), ptr(values), ptr(h_first), ptr(self.hidden), step,
-                                           None if norm is None else ptr(norm.table), 0.0 if norm is None else norm.clip,
-                                           _lib.stream_handle(dev)))
+        bf16 = self.workspace is not None
+        entry = lib.pob_gru_sequence_forward_bf16 if bf16 else lib.pob_gru_sequence_forward
+        check(entry(self.model.gru.handle, S, B, B, ptr(obs), None, ptr(self.hidden), ptr(reset),
+                    ptr(self.theta), ptr(values), ptr(h_first), ptr(self.hidden), step,
+                    None if norm is None else ptr(norm.table), 0.0 if norm is None else norm.clip,
+                    *((ptr(self.workspace),) if bf16 else ()), _lib.stream_handle(dev)))
         return values

@@ -615,6 +615,61 @@ def _recurrent_torch(pre, H, post, act, theta, x, h, reset, cell="gru"):
     return y, state
 
 
+def _recurrent_torch_bf16(pre, H, post, act, theta, x, h, reset):
+    """The definition of the GRU network under ``kernel="bf16"`` (DESIGN.md "Bf16 recurrent window") in
+    torch ops: ``_recurrent_torch`` with every operand of a matrix product rounded to bf16 where it enters
+    the product (the input row, the weights, the dense layers' hidden activations, h in the gates' and the
+    candidate's products); biases, sums, activations and the blend on the unrounded h in the tensors' type."""
+    fn, off = _TORCH_ACT[act], 0
+
+    def dense(v, n_in, n_out):
+        nonlocal off
+        W = theta[off:off + n_in * n_out].view(n_in, n_out)
+        off += n_in * n_out
+        b = theta[off:off + n_out]
+        off += n_out
+        return torch.addmm(b, v, _bf16(W))
+
+    x = _bf16(x)
+    for n_in, n_out in zip(pre[:-1], pre[1:]):
+        x = _bf16(fn(dense(x, n_in, n_out)))
+    I = pre[-1]
+    if reset is not None:
+        h = torch.where(reset.reshape(-1, 1) != 0, torch.zeros_like(h), h)
+    hb = _bf16(h)
+    rz = torch.sigmoid(dense(torch.cat([x, hb], dim=-1), I + H, 2 * H))
+    r, z = rz[:, :H], rz[:, H:]
+    cx = dense(x, I, H)
+    ch = dense(hb, H, H)
+    n = torch.tanh(cx + r * ch)
+    h_new = n + z * (h - n)
+    y, widths = _bf16(h_new), [H] + list(post)
+    for i, (n_in, n_out) in enumerate(zip(widths[:-1], widths[1:])):
+        y = dense(y, n_in, n_out)
+        if i != len(post) - 1:
+            y = _bf16(fn(y))
+    return y, h_new
+
+
+SEQUENCE_KERNELS = ("tile", "bf16")  # the recurrent window's inference kernels (RecurrentValueFunction, apply_sequence)
+
+
+def sequence_kernel(kernel: str, cell: str = "gru") -> str:
+    """``kernel`` if the recurrent window has it; ``ValueError`` otherwise (no ``"resident"`` window exists)."""
+    if kernel not in SEQUENCE_KERNELS:
+        raise ValueError(f"kernel must be one of {list(SEQUENCE_KERNELS)} for the recurrent window, got {kernel!r}")
+    if kernel == "bf16" and cell != "gru":
+        raise ValueError(f"kernel='bf16' runs the GRU window: cell={cell!r} is not supported")
+    return kernel
+
+
+def gru_bf16_workspace(gru: "GRUHandle", device) -> torch.Tensor:
+    """The packed-weight workspace of ``pob_gru_sequence_forward_bf16`` for ``gru`` (contents irrelevant between calls)."""
+    n = C.c_longlong()
+    check(lib.pob_gru_sequence_bf16_workspace_bytes(gru.handle, C.byref(n)))
+    return torch.empty(max(1, n.value // 2), dtype=torch.bfloat16, device=device)
+
+
 def make_recurrent_model(pre_sizes: Sequence[int], hidden_size: int, post_sizes: Sequence[int], obs_size: int,
                          activation: Any = "swish", cell: str = "gru") -> RecurrentModel:
     """``obs_size -> pre_sizes (activation after every layer) -> GRU cell (hidden_size) ->
@@ -685,10 +740,14 @@ def make_recurrent_model(pre_sizes: Sequence[int], hidden_size: int, post_sizes:
         if theta.numel() != gru.param_count:
             raise ValueError(f"theta has {theta.numel()} elements, the network {gru.param_count}")
 
-    def apply_sequence(params, x: torch.Tensor, h0: torch.Tensor, reset: Optional[torch.Tensor] = None):
+    def apply_sequence(params, x: torch.Tensor, h0: torch.Tensor, reset: Optional[torch.Tensor] = None,
+                       kernel: str = "tile"):
         """A window of T steps in torch ops: x (T, M, obs_size), h0 (M, hidden_size), reset (T, M)
         (non-zero: sequence m starts step t from h = 0) -> ``(y (T, M, post_sizes[-1]), h_last)``.
-        Any dtype and device; differentiable by autograd in ``theta``, ``x`` and ``h0``."""
+        Any dtype and device; differentiable by autograd in ``theta``, ``x`` and ``h0``.
+        ``kernel="bf16"`` (GRU only) is the function ``pob_gru_sequence_forward_bf16`` computes, in torch
+        ops: matrix-product operands rounded to bf16, the carried ``h`` not (DESIGN.md "Bf16 recurrent window")."""
+        sequence_kernel(kernel, cell)
         theta = params.theta
         _check_theta(theta)
         if x.dim() != 3 or x.shape[2] != pre[0] or x.shape[0] < 1:
@@ -700,7 +759,11 @@ def make_recurrent_model(pre_sizes: Sequence[int], hidden_size: int, post_sizes:
             raise ValueError(f"reset must be ({T}, {M})")
         h, ys = h0, []
         for t in range(T):
-            y, h = _recurrent_torch(pre, H, post, act, theta, x[t], h, None if reset is None else reset[t], cell)
+            rs = None if reset is None else reset[t]
+            if kernel == "bf16":
+                y, h = _recurrent_torch_bf16(pre, H, post, act, theta, x[t], h, rs)
+            else:
+                y, h = _recurrent_torch(pre, H, post, act, theta, x[t], h, rs, cell)
             ys.append(y)
         return torch.stack(ys), h
 

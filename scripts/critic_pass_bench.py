@@ -9,7 +9,10 @@ events around a replay), after the three have been compared bit for bit:
   sequence   ONE pob_gru_sequence_forward launch (k_gru_seq_infer)
   chained    S pob_gru_forward_norm launches (k_gru_forward), h carried in place through HBM
   train      ONE pob_gru_sequence_forward_train launch (k_gru_seq_forward), which also stores every array
-             the backward pass needs (skipped where `saved` does not fit in --max-saved-gib)
+             the backward pass needs (skipped where `saved` does not fit in --max-saved-gib, or under --no-train)
+  bf16       ONE pob_gru_sequence_forward_bf16 launch (k_gru_pack_bf16 + k_gru_seq_infer_bf16): other values
+             (DESIGN.md "Bf16 recurrent window"), so it is held to the sequence route within the largest
+             difference reported, not bit for bit
 
 then one RecurrentPPOLearner.update with the recurrent critic (one epoch, 32 minibatches of B / 32 envs of
 synthetic rollout buffers, 114 columns) under backward = "torch", ("native", "torch") and "native",
@@ -43,7 +46,7 @@ def _graph(fn):
     return g
 
 
-def bench_pass(name, D, S, B, rounds, warmup, max_saved_gib):
+def bench_pass(name, D, S, B, rounds, warmup, max_saved_gib, with_train=True):
     from po_brax_amd import _lib, jumpy
     from po_brax_amd._lib import check, lib, ptr
     from po_brax_amd.training import networks
@@ -57,7 +60,8 @@ def bench_pass(name, D, S, B, rounds, warmup, max_saved_gib):
                          0.5 + torch.rand(D, device="cuda", generator=gen), torch.ones(D, device="cuda")]).contiguous()
     theta = model.init(jumpy.random_prngkey(1)).theta
     clip = 5.0
-    y = {k: torch.empty((S, B), device="cuda") for k in ("sequence", "chained", "train")}
+    y = {k: torch.empty((S, B), device="cuda") for k in ("sequence", "chained", "train", "bf16")}
+    h_bf16, ws = torch.empty((B, H), device="cuda"), networks.gru_bf16_workspace(model.gru, "cuda")
     h_seq, h_first, h_chain = (torch.empty((B, H), device="cuda") for _ in range(3))
     h_train = torch.empty((B, H), device="cuda")
 
@@ -74,21 +78,27 @@ def bench_pass(name, D, S, B, rounds, warmup, max_saved_gib):
             check(lib.pob_gru_forward_norm(gru, B, ptr(obs[s]), ptr(theta), ptr(reset[s]), ptr(h_chain), ptr(y["chained"][s]),
                                            None, ptr(table), clip, stream()))
 
+    def bf16():
+        check(lib.pob_gru_sequence_forward_bf16(gru, S, B, B, ptr(obs), None, ptr(h0), ptr(reset), ptr(theta), ptr(y["bf16"]),
+                                                None, ptr(h_bf16), S, ptr(table), clip, ptr(ws), stream()))
+
     legs = {"sequence": sequence, "chained": chained}
     need = C.c_longlong()
     check(lib.pob_gru_sequence_saved_bytes(gru, S, B, C.byref(need)))
     out = {"network": name, "obs": D, "hidden": H, "S": S, "B": B, "train_saved_gib": round(need.value / 2 ** 30, 3)}
-    if need.value <= max_saved_gib * 2 ** 30:
+    if with_train and need.value <= max_saved_gib * 2 ** 30:
         saved = torch.empty(need.value // 4, device="cuda")
 
         def train():
             check(lib.pob_gru_sequence_forward_train(gru, S, B, B, ptr(obs), None, ptr(h0), ptr(reset), ptr(theta),
                                                      ptr(y["train"]), ptr(h_train), ptr(saved), ptr(table), clip, stream()))
         legs["train"] = train
-    graphs = {k: _graph(fn) for k, fn in legs.items()}
+    graphs = {k: _graph(fn) for k, fn in {**legs, "bf16": bf16}.items()}
     for g in graphs.values():
         g.replay()
     torch.cuda.synchronize()
+    out["bf16_max_abs_diff_values"] = float((y["bf16"] - y["sequence"]).abs().max())
+    out["bf16_max_abs_diff_hidden"] = float((h_bf16 - h_seq).abs().max())
     same = all(torch.equal(y["sequence"].view(torch.int32), y[k].view(torch.int32)) for k in legs)
     same = same and torch.equal(h_seq.view(torch.int32), h_chain.view(torch.int32))
     out["routes_agree_bitwise"] = bool(same)
@@ -98,6 +108,7 @@ def bench_pass(name, D, S, B, rounds, warmup, max_saved_gib):
     out["chained_over_sequence"] = round(out["chained_ms"] / out["sequence_ms"], 3)
     if "train_ms" in out:
         out["train_over_sequence"] = round(out["train_ms"] / out["sequence_ms"], 3)
+    out["sequence_over_bf16"] = round(out["sequence_ms"] / out["bf16_ms"], 3)
     return out
 
 
@@ -134,6 +145,31 @@ def bench_learner(D, T, B, rounds, warmup):
     return out
 
 
+def bench_replay(T, B, rounds, warmup):
+    """One RecurrentActorRollout replay (ant_heavenhell, masked observations, T steps, actor and critic pass) with the
+    recurrent critic under each window kernel: two rollouts from the same keys, their replays alternating."""
+    from po_brax_amd import envs, jumpy
+    from po_brax_amd import standard_observability_masks as masks
+    from po_brax_amd.rollout import RecurrentActorRollout
+    from po_brax_amd.training import RecurrentValueFunction, networks
+    name, legs, rolls = "ant_heavenhell", {}, {}
+    for kernel in ("tile", "bf16"):
+        env = envs.create(name, batch_size=B, obs_mask=masks.po_env_mask(name, cfrc=False))
+        state = env.reset(jumpy.random_split(jumpy.random_prngkey(3), B))
+        width = env.masked_observation_size
+        p_model = networks.make_recurrent_model([], H, [2 * env.action_size], width)
+        policy = networks.RecurrentTanhPolicy(p_model, p_model.init(jumpy.random_prngkey(5)), jumpy.random_prngkey(6))
+        v_model = networks.make_recurrent_model([], H, [1], width)
+        critic = RecurrentValueFunction(v_model, v_model.init(jumpy.random_prngkey(9)), kernel=kernel)
+        rolls[kernel] = RecurrentActorRollout(env, state, policy, T, masked=True, critic=critic)
+        legs[kernel] = rolls[kernel].replay
+    out = {"env": name, "T": T, "B": B, "critic": f"masked -> GRU {H} -> 1"}
+    out.update(summary(interleaved(legs, rounds, warmup)))
+    out["max_abs_diff_values"] = float((rolls["tile"].values - rolls["bf16"].values).abs().max())
+    out["actor_side_equal"] = bool(torch.equal(rolls["tile"].actions, rolls["bf16"].actions))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=15)
@@ -142,6 +178,8 @@ def main():
     ap.add_argument("--envs", type=int, nargs="+", default=[65536, 4096])
     ap.add_argument("--max-saved-gib", type=float, default=24.0)
     ap.add_argument("--no-learner", action="store_true")
+    ap.add_argument("--no-train", action="store_true", help="leave the train route out of the critic pass")
+    ap.add_argument("--replay", action="store_true", help="also time a rollout replay with the critic under each window kernel")
     ap.add_argument("--learner-rounds", type=int, default=5)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -149,7 +187,10 @@ def main():
            "lib": os.environ.get("POB_LIB", "in-tree"), "passes": []}
     for B in args.envs:
         for name, D in (("masked", 30), ("full", 114)):
-            res["passes"].append(bench_pass(name, D, args.T + 1, B, args.rounds, args.warmup, args.max_saved_gib))
+            res["passes"].append(bench_pass(name, D, args.T + 1, B, args.rounds, args.warmup, args.max_saved_gib,
+                                             not args.no_train))
+    if args.replay:
+        res["rollout_replay"] = bench_replay(args.T, 65536, args.rounds, args.warmup)
     if not args.no_learner:
         res["learner_rounds"] = args.learner_rounds
         res["learner_update"] = bench_learner(114, args.T, 65536, args.learner_rounds, 1)
